@@ -2,12 +2,22 @@
 """bench.py — tokens/sec + mean tokens/forward of multiblock Jacobi decoding (n=32, K=2, r=0.85, pool=4) on a
 Qwen2.5-Coder-7B-shaped model, synthetic HumanEval-shaped prompts, random-init bf16 weights.
 
-  python bench.py --gpus N --steps K --warmup W [--total-prompts M]
+  python bench.py --gpus N --steps K --warmup W [--total-prompts M] [--dump-outputs DIR] [--full]
 
 A "step" is one Jacobi iteration over the rank's batch of prompts: one PyTorch forward over every prompt's rows,
 then the HIP loop body (jf_argmax_scatter -> jf_mb_step -> jf_kv_commit) and one descriptor read-back.  The timed
 region is exactly K steps between barrier+synchronize fences; prompts shard over ranks with no data-path collective and
 rank 0 prints ONE JSON line whose `value` is the whole-job accepted tokens per second.
+
+A plain run does only what the headline needs: set-up, one untimed pre-warm pass (the first min(W + K, 96) iterations), the W
+warm-up and K timed iterations, the line.  --full adds everything else below (the extra objects, config4_strong64).
+--dump-outputs DIR writes what the timed pass computed in its last step as .npy files (per rank r > 0 with a `rank<r>_`
+prefix; float64 unless noted, a few MB): tokens (the token ids of every finished call per prompt, right-padded with -1),
+token_counts, calls and iterations (per-prompt driver counters), descriptor (the loop descriptor after the last step, one row
+per prompt, columns in _native.DESC_FIELDS order), next_input_ids / next_positions / next_row_prompt / next_row_len (the rows
+the last step packed for the next forward: accepted prefixes and new drafts) and logits_sample (float32: 32 rows of the last
+step's bf16 logits, the row indices in logits_rows, drawn with a fixed seed).  Prompts, weights and draw streams are seeded:
+the same arguments give the same inputs.
 
 Ranks: one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the
 ranks are already there (RANK / LOCAL_RANK / WORLD_SIZE in the environment); started as a plain command with
@@ -17,11 +27,11 @@ visible GPUs than ranks is an error, never a silent single-GPU run.
 
 Scaling modes: default WEAK (every rank decodes --prompts-per-gpu prompts, 64 = BASELINE config 4's batch per replica);
 --total-prompts M is STRONG scaling (M prompts sharded over the ranks: M = 64 is config 4 as BASELINE states it, 8 per
-GPU at N = 8).  A weak-scaling run with N > 1 — the driver's plain `--gpus N` — ALSO decodes config 4 as stated (64 prompts
+GPU at N = 8).  With --full, a weak-scaling run with N > 1 (`--gpus N` without --total-prompts) ALSO decodes config 4 as stated (64 prompts
 sharded N-way) in the same process group behind the weak window and reports it as `config4_strong64` (value, ms_per_step,
 tokens_per_forward, roofline, per_rank, per_rank_check); --config4-prompts 0 skips it.
 
-Extra objects on the line:
+Extra objects on the line (--full only):
   roofline      — the argmax launch (the convergence kernel's HBM stream): algorithmic bytes = draft-carrying rows * V * 2
                   per launch over the average launch duration measured with HIP events on the launch stream.
   cpu_baseline  — the CPU oracle (the reference's HF loop + DynamicCache handling restated) with a torch-CPU
@@ -92,6 +102,9 @@ class VerifyTimer:
         self.host_gap = []          # host clock, us: mailbox poll returned -> the next forward is about to be queued (pure host control
                                     # time: unlike `idle` it does not contain other processes' kernels when ranks share a GPU)
         self._seen = None
+        self.keep_logits = False    # --dump-outputs: hold the logits of the latest launch (last_logits, last_valid)
+        self.last_logits = None
+        self.last_valid = 0
 
     def _fill_pool(self, n: int = 512):
         """Events the library will record on (jf_mb_loop_iterate's ev_begin / ev_end): made ahead of the timed window, and
@@ -125,6 +138,8 @@ class VerifyTimer:
             self.launched_rows += int(logits.shape[0])
             self.all_rows.append(int(logits.shape[0]))
             self.all_valid.append(valid)
+            if self.keep_logits:
+                self.last_logits, self.last_valid = logits, valid
 
         def pack_end(batch):
             c = torch.cuda.Event(enable_timing=True)
@@ -188,6 +203,7 @@ def run_steps(dec: MultiblockJacobiDecoder, prompts, warmup: int, steps: int, se
 
     def on_iter(i, d):
         state["tokens_all"] = state.get("tokens_all", 0) + int(d[:, acc_idx].sum())
+        state["last_d"] = d                  # (a host copy of the iteration's descriptor table: the last one is returned)
         if i == warmup and warmup > 0:
             jd.barrier(dev)
             state["acc_at_start"] = state["tokens_all"]
@@ -212,7 +228,47 @@ def run_steps(dec: MultiblockJacobiDecoder, prompts, warmup: int, steps: int, se
         jd.barrier(dev)
         state["t1"] = time.perf_counter()
     tokens = state.get("tokens_all", 0) - state["acc_at_start"]
-    return dict(tokens=tokens, seconds=state["t1"] - state["t0"], iterations=min(iters, total) - warmup, stats=stats)
+    return dict(tokens=tokens, seconds=state["t1"] - state["t0"], iterations=min(iters, total) - warmup, stats=stats,
+                last_descriptor=state.get("last_d"))
+
+
+PREWARM_STEPS = 96       # the untimed pre-warm pass covers the first min(W + K, this) iterations: every GEMM shape of the window
+
+
+DUMP_LOGIT_ROWS = 32     # --dump-outputs: rows of the last step's logits written in full (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, r: dict, info, dec: MultiblockJacobiDecoder, logits=None, valid_rows: int = 0) -> None:
+    """--dump-outputs: what the timed pass computed in its last step — run_steps' stats and descriptor, the token rows the step
+    wrote for the next forward and a seeded sample of the step's logits rows — as float64 (integers, exact) / float32 arrays."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    stats = r["stats"]
+    width = max([len(st.token_ids) for st in stats] + [1])
+    tokens = np.full((len(stats), width), -1.0, dtype=np.float64)
+    for p, st in enumerate(stats):
+        tokens[p, :len(st.token_ids)] = st.token_ids
+    ids, pos, row_prompt, row_len = dec.loop.inputs()[:4]
+    arrays = dict(tokens=tokens,
+                  token_counts=np.array([len(st.token_ids) for st in stats], dtype=np.float64),
+                  calls=np.array([st.calls for st in stats], dtype=np.float64),
+                  iterations=np.array([st.total_iterations for st in stats], dtype=np.float64),
+                  descriptor=np.asarray(r["last_descriptor"], dtype=np.float64),
+                  next_input_ids=ids.cpu().numpy().astype(np.float64),
+                  next_positions=pos.cpu().numpy().astype(np.float64),
+                  next_row_prompt=row_prompt.cpu().numpy().astype(np.float64),
+                  next_row_len=row_len.cpu().numpy().astype(np.float64))
+    if logits is not None and valid_rows > 0:
+        rows = np.sort(np.random.default_rng(0).choice(valid_rows, size=min(DUMP_LOGIT_ROWS, valid_rows), replace=False))
+        arrays["logits_rows"] = rows.astype(np.float64)
+        arrays["logits_sample"] = logits[torch.from_numpy(rows).to(logits.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the 64 MB bound")
+    prefix = f"rank{info.rank}_" if info.rank else ""
+    for name, a in arrays.items():
+        np.save(out / f"{prefix}{name}.npy", a)
 
 
 class StageTimer:
@@ -747,6 +803,11 @@ def main():
     ap.add_argument("--no-tuned-gemms", action="store_true")
     ap.add_argument("--logit-align", type=int, default=0, help="lm_head row count rounded up to this multiple (0 = default)")
     ap.add_argument("--t-align", type=int, default=0, help="forward row length rounded up to this multiple (0 = default: 8 with tuned GEMMs)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the other timing of the launch, "
+                    "scripted acceptance, roofline_by_shape, config4_strong64, the config 2 / config 5 / vs-AR / toy sections and the "
+                    "CPU baseline (each still switched off by its own --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed pass returned in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -799,22 +860,29 @@ def main():
     ta, la = grid_alignment(P, tuned)
     dec = MultiblockJacobiDecoder(model, P, prm, max_seq_len=4096, t_align=args.t_align or ta, logit_align=args.logit_align or la)   # lm_head M stays on the tuned grid (multiples of 8*P)
 
-    # ---- untimed: one pass over the same W + K iterations, so that every library kernel the window launches (the GEMM
-    # shapes change with the rows per step) is loaded before the clock starts; the measured pass below starts again from
-    # the prompts and does all of its work
+    # ---- untimed: one pass over the same first min(W + K, PREWARM_STEPS) iterations, so that every library kernel the window
+    # launches (the GEMM shapes change with the rows per step) is loaded before the clock starts; the measured pass below
+    # starts again from the prompts and does all of its work
     if not args.no_prewarm:
-        run_steps(dec, prompts, args.warmup, args.steps, seed=1234 + info.rank)
+        run_steps(dec, prompts, 0, min(args.warmup + args.steps, PREWARM_STEPS), seed=1234 + info.rank)
     # ---- headline: unmodified random-init model ------------------------------------------------
     with VerifyTimer() as tm:
         tm.valid_rows = lambda: dec.last_valid_rows
+        tm.keep_logits = bool(args.dump_outputs)
         r = run_steps(dec, prompts, args.warmup, args.steps, seed=1234 + info.rank, timer=tm)
         roof = tm.summary()
+    if r["iterations"] != args.steps:
+        raise SystemExit(f"bench.py: the timed pass ended after {r['iterations']} of {args.steps} steps (every prompt stopped: "
+                         "max_seq_len); ask for fewer steps")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r, info, dec, tm.last_logits, tm.last_valid)
+        tm.last_logits = None
     agg = jd.gather_throughput(r["tokens"], r["iterations"] * 1.0, r["seconds"], dev)
     # ---- the same launches timed the OTHER way (one more pass over the same W + K iterations, not part of value): rounds 1-3 recorded the events around the launch
     # (launch + two event packets), round 4 on attaches them to the dispatch (the kernel's own duration, rocprofv3's figure).  Both
     # figures go on the line so that numbers stay comparable across rounds (the library reads the variable per timed call).
     other = None
-    if roof is not None and not args.no_other_timing:          # (every rank: the window's barriers are collective)
+    if args.full and roof is not None and not args.no_other_timing:          # (every rank: the window's barriers are collective)
         was = os.environ.get("JF_VERIFY_EVENTS")
         os.environ["JF_VERIFY_EVENTS"] = "attach" if (was or "")[:1] == "b" else "bracket"
         try:
@@ -839,7 +907,7 @@ def main():
         Path(os.environ["JF_DUMP_LAUNCHES"]).write_text(json.dumps(dict(rows=tm.all_rows, valid=tm.all_valid, V=cfg.vocab_size, esz=2)))
     # ---- same measurement with the synthetic acceptance model -------------------------------------
     scripted = None
-    if not args.no_scripted:
+    if args.full and not args.no_scripted:
         dec.logits_hook = ScriptedAcceptance(cfg.vocab_size, robust_pct=args.robust, vocab_hi=vocab_hi)
         if not args.no_prewarm:
             run_steps(dec, prompts, args.warmup, args.steps, seed=4321 + info.rank)
@@ -864,7 +932,7 @@ def main():
                              "work inside the forward; emulates a Jacobi-Forcing checkpoint's acceptance")
     # ---- the same launch at the literal config-3 / config-4 shapes (1 and 8 prompts per GPU) and at 64 ------------------
     shapes = None
-    if info.world_size == 1 and not args.no_shapes and roof is not None:
+    if args.full and info.world_size == 1 and not args.no_shapes and roof is not None:
         shapes = []
         for Ps in (1, 8, 64):
             if Ps == P:
@@ -886,7 +954,7 @@ def main():
                                    gpu_idle_us_median=rs["idle_us_median"]))
     # ---- N > 1, weak scaling (the driver's plain invocation): config 4 as BASELINE states it, in the same process group
     config4 = None
-    if info.world_size > 1 and not strong and args.config4_prompts > 0 and args.config4_prompts % info.world_size == 0:
+    if args.full and info.world_size > 1 and not strong and args.config4_prompts > 0 and args.config4_prompts % info.world_size == 0:
         config4 = config4_window(model, cfg, prm, tuned, args, info, dev, dev_index, args.config4_prompts, vocab_hi)
     out = None
     if info.rank == 0:
@@ -914,8 +982,9 @@ def main():
                        "gemm_selection": "TunableOp table jacobiforcing_amd/tunableop_mi355x.csv (hipBLASLt/rocBLAS picks for "
                                          "M=64..4096; rows kept on that grid: tuning.grid_alignment)" if tuned else "library default",
                        "dist_backend": jd.backend_name() or "none (single process, no process group)",
-                       "prewarm": "none" if args.no_prewarm else "one untimed pass over the same W + K iterations before the measured "
-                                                                 "pass (loads the library kernels of every GEMM shape the window uses)"},
+                       "prewarm": "none" if args.no_prewarm else (f"one untimed pass over the same first min(W + K, {PREWARM_STEPS}) "
+                                                                  "iterations before the measured pass (loads the library kernels of "
+                                                                  "every GEMM shape the window uses)")},
         }
         # N ranks, verifiable from the line alone: ranks_seen is the communicator's world size (not the environment's), every
         # rank's record names its GPU, devices_distinct counts them (over RCCL a duplicate is refused above, never reported)
@@ -977,7 +1046,7 @@ def main():
             out["scripted_acceptance"] = scripted
         if config4 is not None:
             out["config4_strong64"] = config4
-    if out is not None and info.world_size == 1 and not args.no_sections:
+    if args.full and out is not None and info.world_size == 1 and not args.no_sections:
         del dec
         torch.cuda.empty_cache()
         for key, fn in (("single_block", lambda: single_block_section(model, cfg, tuned)),
@@ -990,7 +1059,7 @@ def main():
             except Exception as e:  # a section must not kill the headline measurement
                 out[key] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
-    if info.rank == 0 and info.world_size == 1 and args.cpu_baseline_seconds > 0:
+    if args.full and info.rank == 0 and info.world_size == 1 and args.cpu_baseline_seconds > 0:
         try:
             # the kernel-level figure first: torch's CPU thread pool keeps spinning after the forward below and would compete
             vk = cpu_verify_kernel(max(int(roof["avg_rows"]), 1), cfg.vocab_size) if roof is not None else None

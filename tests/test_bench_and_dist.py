@@ -42,6 +42,33 @@ def test_run_steps_counts_exactly_k_steps():
         assert r0["iterations"] == 5 and r0["tokens"] >= 5
 
 
+def test_dump_outputs_writes_the_last_step_of_the_timed_pass(tmp_path):
+    """--dump-outputs: the tokens, per-prompt counters, last descriptor and next forward's rows of the timed pass as float64
+    .npy files; the same arguments give the same arrays."""
+    import bench
+    from jacobiforcing_amd.distributed import RankInfo
+    with use_backend("hostsim"):
+        model = tiny_model("cpu", seed=4)
+        V = model.cfg.vocab_size
+        prm = ops.MultiblockParams(n=8, K=2, r=0.85, n_gram_pool_size=4, eos_token_id=None, pad_token_id=V - 2)
+        prompts = [[1, 2, 3, 4, 5, 6, 7], [9, 8, 7, 6, 5]]
+        runs = []
+        for k in range(2):
+            dec = MultiblockJacobiDecoder(model, 2, prm, max_seq_len=512)
+            r = bench.run_steps(dec, prompts, warmup=2, steps=6, seed=1)
+            bench.dump_outputs(tmp_path / str(k), r, RankInfo(0, 1, 0), dec)
+            runs.append({f.stem: np.load(f) for f in (tmp_path / str(k)).glob("*.npy")})
+    a, b = runs
+    assert sorted(a) == ["calls", "descriptor", "iterations", "next_input_ids", "next_positions", "next_row_len", "next_row_prompt",
+                         "token_counts", "tokens"]
+    assert all(x.dtype == np.float64 for x in a.values())
+    assert a["next_input_ids"].shape == a["next_positions"].shape and a["next_input_ids"].shape[0] == a["next_row_len"].shape[0] >= 2
+    assert a["tokens"].shape[0] == 2 and a["descriptor"].shape == (2, len(_native.DESC_FIELDS))
+    for p, n in enumerate(a["token_counts"].astype(int)):
+        assert n >= 1 and (a["tokens"][p, :n] >= 0).all() and (a["tokens"][p, n:] == -1).all()
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_scripted_acceptance_raises_tokens_per_forward():
     """With the synthetic acceptance model the loop accepts several tokens per forward and the output is the
     scripted target sequence (greedy Jacobi == greedy AR of the hooked model)."""
@@ -339,7 +366,7 @@ def test_weak_run_of_several_ranks_also_reports_config_4_as_stated():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(JF_DIST_BACKEND="gloo", JF_FORCE_DEVICE="0", OMP_NUM_THREADS="2")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1", "--model", "tiny",
-                        "--prompts-per-gpu", "4", "--no-scripted", "--no-prewarm", "--cpu-baseline-seconds", "0"], env=env,
+                        "--prompts-per-gpu", "4", "--no-scripted", "--no-prewarm", "--cpu-baseline-seconds", "0", "--full"], env=env,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -418,8 +445,8 @@ def test_bench_single_gpu_through_rccl():
     env.update(JF_DIST_BACKEND="nccl", JF_DIST_FORCE_INIT="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--model", "tiny",
-                        "--prompts-per-gpu", "4", "--no-scripted", "--no-shapes", "--no-sections", "--cpu-baseline-seconds", "0"],
-                       env=env, capture_output=True, text=True, timeout=900)
+                        "--prompts-per-gpu", "4", "--no-scripted", "--no-shapes", "--no-sections", "--cpu-baseline-seconds", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -429,6 +456,35 @@ def test_bench_single_gpu_through_rccl():
     ot = d["roofline"]["other_timing"]                       # both ways of timing the launch on one line
     assert "in front of and behind" in ot["method"] and "attached" in d["roofline"]["timing"]
     assert ot["us_per_launch"] > 0 and ot["launches"] >= 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline alone (no --full objects on the line), runs exactly
+    K timed steps and, with --dump-outputs, writes the timed pass's tokens and last descriptor; a second run writes the same."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "JF_FORCE_DEVICE")}
+    dumps = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--model", "tiny",
+                            "--prompts-per-gpu", "4", "--dump-outputs", str(tmp_path / str(k))], env=env, capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "tokens/s" and d["dtype"] == "bf16"
+        assert all(x["iterations"] == 5 for x in d["per_rank"])
+        for key in ("scripted_acceptance", "roofline_by_shape", "single_block", "nongreedy", "engine_greedy", "vs_ar", "trained_toy",
+                    "cpu_baseline", "config4_strong64"):
+            assert key not in d, key
+        assert "other_timing" not in d["roofline"]
+        dumps.append({f.stem: np.load(f) for f in (tmp_path / str(k)).glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["calls", "descriptor", "iterations", "logits_rows", "logits_sample", "next_input_ids", "next_positions",
+                         "next_row_len", "next_row_prompt", "token_counts", "tokens"]
+    assert a["logits_sample"].dtype == np.float32 and a["logits_sample"].shape == (len(a["logits_rows"]), 4096)
+    assert a["tokens"].dtype == np.float64 and a["tokens"].shape[0] == 4 and a["descriptor"].shape == (4, len(_native.DESC_FIELDS))
+    assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_forced_single_rank_group_over_gloo(tmp_path):

@@ -15,7 +15,7 @@ i=0
 for grp in "GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA_RDREQ_sum TCC_EA_RDREQ_32B_sum" "TCP_TCC_READ_REQ_sum"; do
     i=$((i+1))
     JF_DUMP_LAUNCHES=$OUT/launches_insitu_$i.json timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/insitu_$i -o run -- \
-        python bench.py --steps 12 --warmup 2 --no-scripted --no-shapes --no-sections --cpu-baseline-seconds 0 > $OUT/insitu_$i.log 2>&1
+        python bench.py --full --steps 12 --warmup 2 --no-scripted --no-shapes --no-sections --cpu-baseline-seconds 0 > $OUT/insitu_$i.log 2>&1
     timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/synth_$i -o run -- \
         python tools/verify_trace.py --prompts 64 --iters 14 > $OUT/synth_$i.log 2>&1
 done

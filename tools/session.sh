@@ -39,9 +39,9 @@ rs_ab)                # microbenchmark of jf_rs_probs over experiment builds: ba
     ;;
 ranks8)               # what eight ranks do to one host: the real model, 8 prompts per rank, 1 rank vs 8 ranks sharing the one GPU (gloo)
     COMMON="--steps 40 --warmup 8 --no-scripted --no-shapes --no-sections --cpu-baseline-seconds 0"
-    timeout 900 python bench.py --gpus 1 --prompts-per-gpu 8 $COMMON > $O/ranks1.json 2> $O/ranks1.err
-    JF_DIST_BACKEND=gloo JF_FORCE_DEVICE=0 timeout 1500 python bench.py --gpus 8 --total-prompts 64 $COMMON > $O/ranks8.json 2> $O/ranks8.err
-    JF_PIN_CPUS=0 JF_DIST_BACKEND=gloo JF_FORCE_DEVICE=0 timeout 1500 python bench.py --gpus 8 --total-prompts 64 $COMMON > $O/ranks8_unpinned.json 2> $O/ranks8_unpinned.err
+    timeout 900 python bench.py --full --gpus 1 --prompts-per-gpu 8 $COMMON > $O/ranks1.json 2> $O/ranks1.err
+    JF_DIST_BACKEND=gloo JF_FORCE_DEVICE=0 timeout 1500 python bench.py --full --gpus 8 --total-prompts 64 $COMMON > $O/ranks8.json 2> $O/ranks8.err
+    JF_PIN_CPUS=0 JF_DIST_BACKEND=gloo JF_FORCE_DEVICE=0 timeout 1500 python bench.py --full --gpus 8 --total-prompts 64 $COMMON > $O/ranks8_unpinned.json 2> $O/ranks8_unpinned.err
     python tools/idle_gap_table.py $O/ranks1.json $O/ranks8.json $O/ranks8_unpinned.json | tee $O/idle_gap.txt
     ;;
 dist_tests)           # the N > 1 line's evidence fields on the GPU box
@@ -83,19 +83,19 @@ gputests)             # the whole GPU suite + smoke
     timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
     ;;
 bench)                # the driver's command (+ extra flags): bash tools/session.sh bench [flags]
-    timeout 1500 python bench.py --steps 20 --warmup 5 "$@" > $O/bench.json 2> $O/bench.err
+    timeout 1500 python bench.py --full --steps 20 --warmup 5 "$@" > $O/bench.json 2> $O/bench.err
     python tools/bench_brief.py $O/bench.json
     ;;
 timing_ab)            # events attached to the dispatch against events recorded around the launch, one box
-    timeout 900 python bench.py --steps 20 --warmup 5 --no-shapes --cpu-baseline-seconds 0 > $O/bench_dispatch.json 2> $O/bench_dispatch.err
-    JF_VERIFY_EVENTS=bracket timeout 900 python bench.py --steps 20 --warmup 5 --no-shapes --cpu-baseline-seconds 0 > $O/bench_bracket.json 2> $O/bench_bracket.err
+    timeout 900 python bench.py --full --steps 20 --warmup 5 --no-shapes --cpu-baseline-seconds 0 > $O/bench_dispatch.json 2> $O/bench_dispatch.err
+    JF_VERIFY_EVENTS=bracket timeout 900 python bench.py --full --steps 20 --warmup 5 --no-shapes --cpu-baseline-seconds 0 > $O/bench_bracket.json 2> $O/bench_bracket.err
     for n in dispatch bracket; do echo "== $n"; python tools/bench_brief.py $O/bench_$n.json; done | tee $O/timing_ab.txt
     ;;
 item_wgs)             # how many item workgroups walk the convergence launch's list (JF_VERIFY_ITEM_WGS) x chunks per row (JF_ARGMAX_ITEMS)
     for CFG in "0 0" "1536 0" "1024 0" "768 0" "512 0" "256 0" "1024 3000" "1024 6000"; do
         set -- $CFG
         echo "== item workgroups $1  JF_ARGMAX_ITEMS $2"
-        env JF_VERIFY_ITEM_WGS=$1 $( [ $2 != 0 ] && echo JF_ARGMAX_ITEMS=$2 ) timeout 600 python bench.py --steps 20 --warmup 5 --no-shapes --no-sections --cpu-baseline-seconds 0 2>/dev/null > $O/b.json
+        env JF_VERIFY_ITEM_WGS=$1 $( [ $2 != 0 ] && echo JF_ARGMAX_ITEMS=$2 ) timeout 600 python bench.py --full --steps 20 --warmup 5 --no-shapes --no-sections --cpu-baseline-seconds 0 2>/dev/null > $O/b.json
         python tools/bench_brief.py $O/b.json
     done | tee $O/item_wgs.txt
     ;;
@@ -130,11 +130,11 @@ engine_step)          # jf_engine_step as one launch against its two launches (r
     ;;
 rocprof_bench)        # rocprofv3 --kernel-trace --stats of the bench command + per-grid / per-class / per-dispatch views
     rm -rf /tmp/prof_bench /tmp/prof_head
-    (cd /tmp && JF_DUMP_LAUNCHES=$ROOT/$O/launches.json timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python $ROOT/bench.py --steps 20 --warmup 5 --no-shapes --no-sections --cpu-baseline-seconds 0 > $ROOT/$O/rocprof_bench.log 2>&1)
+    (cd /tmp && JF_DUMP_LAUNCHES=$ROOT/$O/launches.json timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no-shapes --no-sections --cpu-baseline-seconds 0 > $ROOT/$O/rocprof_bench.log 2>&1)
     cp $(find /tmp/prof_bench -name "*kernel_stats.csv" | head -1) $O/rocprof_bench_kernel_stats.csv
     python tools/verify_by_grid.py /tmp/prof_bench > $O/verify_by_grid.txt 2>&1
     python tools/kernel_classes.py /tmp/prof_bench > $O/kernel_classes.txt 2>&1
-    (cd /tmp && JF_DUMP_LAUNCHES=$ROOT/$O/launches_headline.json timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_head -- python $ROOT/bench.py --steps 20 --warmup 5 --no-shapes --no-sections --no-scripted --no-prewarm --cpu-baseline-seconds 0 > /dev/null 2>&1)
+    (cd /tmp && JF_DUMP_LAUNCHES=$ROOT/$O/launches_headline.json timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_head -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no-shapes --no-sections --no-scripted --no-prewarm --cpu-baseline-seconds 0 > /dev/null 2>&1)
     python tools/verify_per_dispatch.py /tmp/prof_head $O/launches_headline.json > $O/verify_per_dispatch_headline.txt 2>&1
     tail -5 $O/verify_per_dispatch_headline.txt; head -30 $O/kernel_classes.txt
     ;;
@@ -153,10 +153,10 @@ soak)                 # the randomised parity sweeps at JF_FUZZ_SCALE (default 1
     ;;
 evidence)             # the round's evidence in one call: suite, smoke, the driver's bench line, RCCL n=1, strong 64, 1 / 8 prompts, profiles
     bash "$0" gputests
-    timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; python tools/bench_brief.py $O/bench_n1.json
-    JF_DIST_BACKEND=nccl JF_DIST_FORCE_INIT=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29655 timeout 900 python bench.py --steps 20 --warmup 5 --no-shapes --no-sections --no-scripted --cpu-baseline-seconds 0 > $O/bench_rccl_n1.json 2> $O/bench_rccl_n1.err
-    timeout 600 python bench.py --steps 20 --warmup 5 --total-prompts 64 --no-sections --cpu-baseline-seconds 0 > $O/bench_strong64.json 2>/dev/null
-    for P in 1 8; do timeout 600 python bench.py --prompts-per-gpu $P --steps 48 --warmup 8 --no-shapes --no-sections --cpu-baseline-seconds 0 > $O/bench_p$P.json 2>/dev/null; done
+    timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; python tools/bench_brief.py $O/bench_n1.json
+    JF_DIST_BACKEND=nccl JF_DIST_FORCE_INIT=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29655 timeout 900 python bench.py --full --steps 20 --warmup 5 --no-shapes --no-sections --no-scripted --cpu-baseline-seconds 0 > $O/bench_rccl_n1.json 2> $O/bench_rccl_n1.err
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --total-prompts 64 --no-sections --cpu-baseline-seconds 0 > $O/bench_strong64.json 2>/dev/null
+    for P in 1 8; do timeout 600 python bench.py --full --prompts-per-gpu $P --steps 48 --warmup 8 --no-shapes --no-sections --cpu-baseline-seconds 0 > $O/bench_p$P.json 2>/dev/null; done
     bash "$0" rocprof_bench; cp gpurun_out/rocprof_bench/* $O/ 2>/dev/null
     bash "$0" pmc_verify; cp gpurun_out/pmc/pmc_verify.json $O/ 2>/dev/null
     ;;

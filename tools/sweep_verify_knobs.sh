@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 run() {
-  env "$@" timeout 900 python bench.py --steps 20 --warmup 5 --cpu-baseline-seconds 0 --no-shapes > /tmp/b.json 2>/dev/null
+  env "$@" timeout 900 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-seconds 0 --no-shapes > /tmp/b.json 2>/dev/null
   python - "$*" <<'PY'
 import json,sys
 d=json.loads([l for l in open("/tmp/b.json") if l.startswith("{")][0])
