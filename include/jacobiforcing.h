@@ -605,6 +605,26 @@ JF_API int jf_rs_onpolicy_step(const void *logits, int dtype, int64_t V, int64_t
                         void *workspace /* jf_rs_step_workspace_bytes(R) */, size_t workspace_bytes,
                         const jf_rs_filter_row *filt /* nullable: jf_rs_filter's records of the R rows */, void *stream);
 
+/* The same step for G sequences in one call (lock-step rollouts): five launches whatever G is.  The rows are a
+ * rectangle [G, Lm], flat row g * Lm + t; sequence g uses its first n_rows[g] rows (1..Lm), the rest is padding that the
+ * step never reads from the logits and that consumes no draw.  logits / p_draft / row_max / row_sumexp / packed / filt
+ * cover all G * Lm rows (jf_rs_probs / jf_rs_filter run on the rectangle as it is); packed is re-zeroed for all of them.
+ * Every sequence has its own randomness: its uniforms are u_stream[stream_off[g][0] .. + stream_len[g][0]), its multinomial
+ * draws m_stream[stream_off[g][1] .. + stream_len[g][1]), consumed cyclically from cursors[g][0] / cursors[g][1], which are
+ * advanced.  Per sequence every decision, committed[g][..], redraft[g][..] and rows[g] are what jf_rs_onpolicy_step gives
+ * for that sequence alone.  n_rows, stream_off and stream_len are device arrays: a sequence whose row count is outside
+ * 1..Lm, or whose slice is empty, gets rows[g].n_committed = -1 and nothing else of it is touched.
+ */
+JF_API int jf_rs_onpolicy_step_batch(const void *logits, int dtype, int64_t V, int64_t row_stride, const int64_t *proposed /* [G, Lm] */,
+                        const int32_t *n_rows /* [G] */, int G, int Lm,
+                        const float *p_draft, const float *row_max, const float *row_sumexp, uint64_t *packed,
+                        float temperature, const int32_t *stop_ids, int n_stop,
+                        const float *u_stream, const float *m_stream,
+                        const int64_t *stream_off /* [G, 2] */, const int64_t *stream_len /* [G, 2] */, int64_t *cursors /* [G, 2] */,
+                        int64_t *committed /* [G, Lm] */, int64_t *redraft /* [G, Lm] */, jf_op_row *rows /* [G] */,
+                        void *workspace /* jf_rs_step_workspace_bytes(G * Lm) */, size_t workspace_bytes,
+                        const jf_rs_filter_row *filt /* nullable: jf_rs_filter's records of the G * Lm rows */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,13 @@ fresh multinomial sample of every not yet accepted position (JDO:465-477) run on
 once, ``jf_rs_onpolicy_step`` does the sequential part and the per-row inverse-CDF draws; one read-back per forward instead
 of two ``.item()`` syncs per position.  Randomness comes from pre-drawn streams consumed in the reference's order
 (``torch.rand`` JDO:306, ``torch.multinomial`` JDO:154, ``random.choice`` JDO:266); ``set_streams`` injects them.
+
+LOCK-STEP (``lockstep=True``, beyond the reference, whose JDO:529-583 walks the batch one sequence at a time): block round k
+opens block k of every sequence that is still active; while any of them is open, ONE forward carries all open rows and
+``jf_rs_onpolicy_step_batch`` steps them together.  Randomness is per sequence (``set_streams_per_sequence``), so sequence i
+gets exactly what the sequential path gives for ``[seqs[i]]`` alone with its streams.  Rows of different pending lengths are
+right-padded with PAD to the longest of their group (the model is causal: a row's own logits do not see its tail) and the
+KV is trimmed by the padded length; rows are grouped by (temperature, top_k, top_p), one forward and one step per group.
 """
 from __future__ import annotations
 
@@ -133,6 +140,13 @@ class JacobiDecoderNonGreedyOnPolicy:
         self._unis = self._multi = None
         self._cur = [0, 0]               # uniforms, multinomial draws consumed
         self._stepper: Optional[ops.OnPolicyStepper] = None
+        # lock-step: per-sequence streams (rnds, uniforms, multinomials), whether they were drawn here, draws consumed
+        self._seq_streams: Optional[Tuple[list, list, list]] = None
+        self._seq_streams_drawn = False
+        self.cursors_per_sequence: List[List[int]] = []
+        self._batch_stepper: Optional[ops.OnPolicyBatchStepper] = None
+        self.max_forward_positions: Optional[int] = None      # positions the caller's cache holds per sequence (None: no bound)
+        self.lockstep_forwards: List[Tuple[int, int, int]] = []   # (rows, padded length, valid rows) of the last lock-step call's forwards
 
     # ------------------------------------------------------------------------------- randomness
     def set_streams(self, rnd, uniforms, multinomial) -> None:
@@ -143,6 +157,32 @@ class JacobiDecoderNonGreedyOnPolicy:
         self._multi = np.asarray(multinomial, dtype=np.float32).copy()
         self._cur = [0, 0]
         self._stepper = None
+
+    def set_streams_per_sequence(self, rnds, uniforms, multinomials) -> None:
+        """Lock-step randomness: three lists of one entry per sequence of the batch, each entry what ``set_streams`` takes."""
+        if not (len(rnds) == len(uniforms) == len(multinomials)):
+            raise ValueError("set_streams_per_sequence needs three lists of the same length (one entry per sequence)")
+        self._seq_streams = (list(rnds), [np.asarray(u, dtype=np.float32).copy() for u in uniforms],
+                             [np.asarray(m, dtype=np.float32).copy() for m in multinomials])
+        self._seq_streams_drawn = False
+        self.cursors_per_sequence = [[0, 0] for _ in rnds]
+        self._batch_stepper = None
+
+    def _ensure_batch(self, B: int, L: int) -> ops.OnPolicyBatchStepper:
+        if self._seq_streams is None or (self._seq_streams_drawn and len(self._seq_streams[0]) != B):
+            self.set_streams_per_sequence([random.Random(random.getrandbits(64)) for _ in range(B)],
+                                          [torch.rand(_STREAM_LEN).numpy() for _ in range(B)],
+                                          [torch.rand(_STREAM_LEN).numpy() for _ in range(B)])
+            self._seq_streams_drawn = True
+        if len(self._seq_streams[0]) != B:
+            raise ValueError(f"set_streams_per_sequence gave {len(self._seq_streams[0])} streams, the batch has {B} sequences")
+        st = self._batch_stepper
+        if st is None or st.max_L < L:
+            st = ops.OnPolicyBatchStepper(B, max(L, 64 if st is None else st.max_L), self.device, self._seq_streams[1],
+                                          self._seq_streams[2], self.stop_token_ids)
+            st.cursors.copy_(torch.tensor(self.cursors_per_sequence, dtype=torch.int64).view(B, 2))
+            self._batch_stepper = st
+        return st
 
     def _ensure(self, L: int) -> ops.OnPolicyStepper:
         if self._unis is None:
@@ -169,15 +209,16 @@ class JacobiDecoderNonGreedyOnPolicy:
             return self.forward_step(seq, draft)
         return self.forward_step_batch([seq], draft)
 
-    def _init_block_draft_from_prompt(self, prompt_ids: List[int], block_len: int) -> List[int]:
+    def _init_block_draft_from_prompt(self, prompt_ids: List[int], block_len: int, rnd=None) -> List[int]:
         """JDO:254-266: sample from the prompt's tokens with replacement, pads excluded."""
         if block_len <= 0:
             return []
+        rnd = self._rnd if rnd is None else rnd
         pad = self.pad_token_id
         choices = [int(t) for t in prompt_ids if int(t) != pad]
         if not choices:
-            return [self._rnd.randrange(self.vocab_size) for _ in range(block_len)]
-        return [self._rnd.choice(choices) for _ in range(block_len)]
+            return [rnd.randrange(self.vocab_size) for _ in range(block_len)]
+        return [rnd.choice(choices) for _ in range(block_len)]
 
     # ------------------------------------------------------------------------------- one block (JDO:331-488)
     @torch.inference_mode()
@@ -247,10 +288,112 @@ class JacobiDecoderNonGreedyOnPolicy:
             blk.snapshot()
         return blk.trajectory, appended_total, fwd_used, blk.stopped
 
+    # ------------------------------------------------------------------------------- one block round, all sequences together
+    def _lockstep_groups(self, seqs: List[Sequence], rows: List[int], blocks: Dict[int, _BlockState]) -> List[List[int]]:
+        """The open rows as forward groups: by (temperature, top_k, top_p) in order of first appearance; a row that the group's
+        padded length would push over ``max_forward_positions`` is stepped alone (its own forward fits, as it would today)."""
+        by_key: Dict[tuple, List[int]] = {}
+        for i in rows:
+            sp = getattr(seqs[i], "sampling_params", None)
+            temperature = float(getattr(sp, "temperature", 1.0)) if sp is not None else 1.0
+            by_key.setdefault((temperature,) + ops.active_filters(sp, self.vocab_size), []).append(i)
+        bound, groups = self.max_forward_positions, []
+        for members in by_key.values():
+            alone: List[int] = []
+            while bound is not None and len(members) > 1:
+                Lm = max(blocks[i].gen_len - blocks[i].accepted for i in members)
+                over = [i for i in members if len(seqs[i]) + Lm > bound and blocks[i].gen_len - blocks[i].accepted < Lm]
+                if not over:
+                    break
+                alone += over
+                members = [i for i in members if i not in over]
+            groups.append(members)
+            groups += [[i] for i in alone]
+        return groups
+
+    @torch.inference_mode()
+    def _run_blocks_lockstep(self, seqs: List[Sequence], rows: List[int], block_lens: List[int], budgets: List[int],
+                             completion_start_lens: List[int]) -> Dict[int, Tuple[List[List[int]], int, int, bool]]:
+        """``_run_one_block`` for the sequences ``rows`` of the batch at once: {i: (trajectory, appended, forwards, stopped)}."""
+        if not rows:
+            return {}
+        st = self._ensure_batch(len(seqs), max(int(block_lens[i]) for i in rows) + 1)
+        rnds = self._seq_streams[0]
+        bm, pad = self.block_manager, self.pad_token_id
+        blocks: Dict[int, _BlockState] = {}
+        fwd_used, appended = {i: 0 for i in rows}, {i: 0 for i in rows}
+        for i in rows:                                                               # every block opens from the round's start state
+            blk = _BlockState(int(block_lens[i]), min(int(block_lens[i]), int(budgets[i])), pad, self.stop_token_ids)
+            blk.start(self._init_block_draft_from_prompt(list(seqs[i].token_ids), blk.gen_len, rnds[i]))
+            blocks[i] = blk
+        while True:
+            open_rows = [i for i in rows if blocks[i].open()]
+            if not open_rows:
+                break
+            for group in self._lockstep_groups(seqs, open_rows, blocks):
+                gs = [seqs[i] for i in group]
+                for seq in gs:
+                    if not seq.token_ids:
+                        seq.token_ids = [pad]
+                proposed = [blocks[i].pending() for i in group]
+                n_rows = [len(p) for p in proposed]
+                Lm = max(n_rows)
+                draft = torch.tensor([[int(seq.token_ids[-1])] + p + [pad] * (Lm - len(p)) for seq, p in zip(gs, proposed)],
+                                     dtype=torch.long, device=self.device)
+                for seq, p in zip(gs, proposed):
+                    seq.draft_tokens = [int(seq.token_ids[-1])] + p
+                logits = self.forward_step_batch(gs, draft)                          # [G, Lm, V]
+                self.lockstep_forwards.append((len(group), Lm, sum(n_rows)))
+                if logits.ndim != 3 or int(logits.size(0)) != len(group) or int(logits.size(1)) != Lm:
+                    raise ValueError(f"forward must return logits [{len(group)}, {Lm}, vocab], got {tuple(logits.shape)}")
+                V = int(logits.size(-1))
+                bad = next((x for p in proposed for x in p if not 0 <= x < V), None)   # JDO:298-301
+                if bad is not None:
+                    raise ValueError(f"Token index {bad} out of bounds for vocab size {V}. "
+                                     "This may indicate a mismatch between model vocab and tokenizer vocab.")
+                sp = getattr(gs[0], "sampling_params", None)
+                temperature = float(getattr(sp, "temperature", 1.0)) if sp is not None else 1.0
+                top_k, top_p = ops.active_filters(sp, self.vocab_size)
+                recs, committed_all, redraft_all = st.step(draft[:, 1:], n_rows, logits, temperature, group, top_k, top_p)
+                for i, seq, prop, row, committed, redraft in zip(group, gs, proposed, recs, committed_all, redraft_all):
+                    blk = blocks[i]
+                    self.cursors_per_sequence[i][0] += row["n_uniforms"]
+                    self.cursors_per_sequence[i][1] += row["n_bonus_draws"] + row["n_redraft"]
+                    stop_hit = bool(row["stop_hit"])
+                    if not committed:
+                        committed, stop_hit = [prop[0]], prop[0] in blk.stop
+                    seq.extend_tokens(committed)                                     # JDO:412-416
+                    if bm is not None:
+                        bm.may_append_batch(seq, len(committed))
+                        if Lm > len(committed):
+                            bm.trim_kv_only_fast(seq, Lm - len(committed))          # the forward cached Lm positions behind the seed
+                    fwd_used[i] += 1
+                    appended[i] += len(committed)
+                    seq.clear_draft()
+                    if len(seq) != seq.num_cached_tokens:
+                        raise RuntimeError(f"Invariant violated: len(token_ids)={len(seq)} != num_cached_tokens={seq.num_cached_tokens}")
+                    first_new = blk.accept(committed)
+                    if stop_hit:                                                     # JDO:439-463
+                        kept = _truncate_after_stop(list(seq.token_ids), completion_start_lens[i], self.stop_token_ids)
+                        dropped = len(seq.token_ids) - len(kept)
+                        if dropped:
+                            seq.token_ids = kept
+                            if bm is not None:
+                                bm.trim_kv_only_fast(seq, dropped)
+                        blk.close_at_stop(first_new)
+                    elif blk.accepted < blk.gen_len:                                 # JDO:465-477 (samples drawn on the GPU)
+                        blk.refill(redraft[len(committed):])
+                    blk.snapshot()
+        return {i: (blocks[i].trajectory, appended[i], fwd_used[i], blocks[i].stopped) for i in rows}
+
     # ------------------------------------------------------------------------------- records (JDO:494-614)
     @torch.inference_mode()
     def generate_rollout_records_batch(self, seqs: List[Sequence], n_token_seq_len: Optional[int] = None,
-                                       return_metrics: bool = False) -> object:
+                                       return_metrics: bool = False, lockstep: bool = False) -> object:
+        """``lockstep=True``: every block round steps all active sequences in one forward per group (module docstring); needs
+        ``forward_step_batch`` and per-sequence randomness (``set_streams_per_sequence``, else drawn here)."""
+        if lockstep and self.forward_step_batch is None:
+            raise ValueError("lockstep=True needs forward_step_batch: one forward carries every open row of the batch")
         if not seqs:
             return ([], []) if return_metrics else []
         B = len(seqs)
@@ -260,6 +403,8 @@ class JacobiDecoderNonGreedyOnPolicy:
         max_blocks = [int(c[1]) for c in cfgs]
         budgets = [int(c[2]) for c in cfgs]
         stopped = [False] * B
+        if lockstep:
+            self.lockstep_forwards = []
         num_blocks_done, num_forwards, total_generated = [0] * B, [0] * B, [0] * B
         data_ids = [_infer_data_id(seqs[i], fallback=f"data_{i}") for i in range(B)]
         per_seq_out: List[Dict[int, Dict[str, object]]] = [dict() for _ in range(B)]
@@ -267,14 +412,23 @@ class JacobiDecoderNonGreedyOnPolicy:
             active = [i for i in range(B) if not stopped[i] and num_blocks_done[i] < max_blocks[i] and budgets[i] > 0]
             if not active:
                 break
+            round_out = None
+            if lockstep:
+                prompts_trim = {i: _trim_left_padding(list(seqs[i].token_ids), self.pad_token_id) for i in active}
+                round_out = self._run_blocks_lockstep(seqs, [i for i in active if block_lens[i] > 0], block_lens, budgets,
+                                                      completion_start_lens)
             for i in active:
                 seq, k = seqs[i], int(num_blocks_done[i])
                 if block_lens[i] <= 0:
                     stopped[i] = True
                     continue
-                prompt_ids_trim = _trim_left_padding(list(seq.token_ids), self.pad_token_id)
-                traj, appended_now, fwd_used, stop_hit = self._run_one_block(seq, block_lens[i], budgets[i],
-                                                                             completion_start_lens[i])
+                if round_out is not None:
+                    prompt_ids_trim = prompts_trim[i]
+                    traj, appended_now, fwd_used, stop_hit = round_out[i]
+                else:
+                    prompt_ids_trim = _trim_left_padding(list(seq.token_ids), self.pad_token_id)
+                    traj, appended_now, fwd_used, stop_hit = self._run_one_block(seq, block_lens[i], budgets[i],
+                                                                                 completion_start_lens[i])
                 num_blocks_done[i] += 1
                 num_forwards[i] += int(fwd_used)
                 total_generated[i] += int(appended_now)
@@ -307,8 +461,10 @@ class JacobiDecoderNonGreedyOnPolicy:
         return per_seq_out, metrics
 
     @torch.inference_mode()
-    def generate_rollout_records(self, seq: Sequence, n_token_seq_len: Optional[int] = None, return_metrics: bool = False):
-        out = self.generate_rollout_records_batch([seq], n_token_seq_len=n_token_seq_len, return_metrics=return_metrics)
+    def generate_rollout_records(self, seq: Sequence, n_token_seq_len: Optional[int] = None, return_metrics: bool = False,
+                                 lockstep: bool = False):
+        out = self.generate_rollout_records_batch([seq], n_token_seq_len=n_token_seq_len, return_metrics=return_metrics,
+                                                  lockstep=lockstep)
         if not return_metrics:
             return out[0] if out else {}
         records, metrics = out

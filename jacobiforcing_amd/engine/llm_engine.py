@@ -69,6 +69,7 @@ class LLMEngine:
                 seq._rollout_records = result
                 if seq in self.scheduler.running:
                     self.scheduler.running.remove(seq)
+                self.scheduler.block_manager.deallocate(seq)      # (the reference keeps them, ENG:106-110: a second rollout batch then finds the pool smaller)
                 self.model_runner.release(seq)
             return [(seq.seq_id, seq._rollout_records) for seq in seqs], (-num_new if num_new > 0 else 0)
         token_ids = result

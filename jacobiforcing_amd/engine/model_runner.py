@@ -414,6 +414,7 @@ class ModelRunner:
                     block_manager=self.block_manager, forward_step=self._jacobi_forward_step,
                     forward_step_batch=self._jacobi_forward_step_batch, eos_token_id=self.config.eos,
                     pad_token_id=self.config.pad, vocab_size=self.config.hf_config.vocab_size, device=self.device)
+                self.jacobi_decoder.max_forward_positions = self.config.max_model_len      # lock-step padding stays inside the cache
             return
         temps = [float(getattr(s, "temperature", 0.0)) for s in jac]
         all_greedy, all_ng = all(t == 0.0 for t in temps), all(t > 0.0 for t in temps)
@@ -523,7 +524,9 @@ class ModelRunner:
                 if not isinstance(self.jacobi_decoder, JacobiDecoderNonGreedyOnPolicy):
                     raise RuntimeError("On-policy decoder not initialized correctly. Expected JacobiDecoderNonGreedyOnPolicy "
                                        f"but got {type(self.jacobi_decoder)}")
+                # lock-step rollouts: opt-in, planted on the request's SamplingParams like top_k / top_p (no such field upstream)
+                lockstep = any(bool(getattr(getattr(s, "sampling_params", None), "jacobi_lockstep", False)) for s in seqs)
                 return self.jacobi_decoder.generate_rollout_records_batch(
-                    seqs, n_token_seq_len=getattr(seqs[0], "jacobi_block_len", 64), return_metrics=False)
+                    seqs, n_token_seq_len=getattr(seqs[0], "jacobi_block_len", 64), return_metrics=False, lockstep=lockstep)
             return self.jacobi_decoder.generate_chunk_batch(seqs)
         return self._run_autoregressive(seqs, is_prefill)

@@ -1234,3 +1234,100 @@ class OnPolicyStepper:
         row = dict(zip(N.OP_FIELDS, self.row_host.tolist()))
         n = row["n_committed"]
         return row, self.out_host[0, :n].tolist(), self.out_host[1, :R].tolist()
+
+
+class OnPolicyBatchStepper:
+    """jf_rs_probs [+ jf_rs_filter] + jf_rs_onpolicy_step_batch for a group of sequences per call (lock-step rollouts): the
+    number of launches does not depend on the group, one pinned read-back and one synchronise per forward.  Every sequence
+    has its own two streams (concatenated once on the device) and its own two cursors, which stay on the device between
+    forwards (``self.cursors`` [max_rows, 2]: uniforms, multinomial)."""
+
+    def __init__(self, max_rows: int, max_L: int, device, u_streams, m_streams, stop_ids: Sequence[int]):
+        dev = torch.device(device)
+        self.device, self.max_rows, self.max_L = dev, int(max_rows), int(max_L)
+        if len(u_streams) != self.max_rows or len(m_streams) != self.max_rows:
+            raise ValueError("OnPolicyBatchStepper needs one uniform and one multinomial stream per sequence")
+        n = self.max_rows * self.max_L
+        self.packed = new_packed(n, dev)
+        f32 = lambda k: torch.zeros((k,), dtype=torch.float32, device=dev)
+        self.p_draft, self.row_max, self.row_sumexp = f32(n), f32(n), f32(n)
+        self.ws = torch.zeros((n * 16 * 2,), dtype=torch.float32, device=dev)     # grown to jf_rs_workspace_bytes(R, V) on demand
+        self.step_ws = torch.zeros((int(N.lib().jf_rs_step_workspace_bytes(n)) // 8 + 2,), dtype=torch.float64, device=dev)
+        # one buffer for everything a forward reads back: committed [G, Lm] ⧺ redraft [G, Lm] ⧺ the G records (4 words each)
+        words = 2 * n + self.max_rows * (N.OP_ROW_INTS // 2)
+        self.out = torch.zeros((words,), dtype=torch.int64, device=dev)
+        self.out_host = torch.zeros((words,), dtype=torch.int64, pin_memory=dev.type == "cuda")
+        us = [np.asarray(u, dtype=np.float32).reshape(-1) for u in u_streams]
+        ms = [np.asarray(m, dtype=np.float32).reshape(-1) for m in m_streams]
+        if any(a.size == 0 for a in us + ms):
+            raise ValueError("OnPolicyBatchStepper: empty random stream")
+        self.u_stream = torch.from_numpy(np.concatenate(us)).to(dev)
+        self.m_stream = torch.from_numpy(np.concatenate(ms)).to(dev)
+        starts = lambda arrs: np.cumsum([0] + [a.size for a in arrs[:-1]])
+        self.stream_off = torch.from_numpy(np.stack([starts(us), starts(ms)], 1).astype(np.int64)).to(dev)             # [max_rows, 2]
+        self.stream_len = torch.from_numpy(np.array([[a.size, b.size] for a, b in zip(us, ms)], dtype=np.int64)).to(dev)
+        self.stop_ids = torch.tensor([int(x) for x in stop_ids], dtype=torch.int32, device=dev)
+        self.cursors = torch.zeros((self.max_rows, 2), dtype=torch.int64, device=dev)
+        self.filter: Optional[RowFilter] = None
+
+    def step(self, proposed: torch.Tensor, n_rows: Sequence[int], logits: torch.Tensor, temperature: float,
+             seq_index: Sequence[int], top_k: int = 0, top_p: float = 0.0):
+        """proposed [G, Lm] int64 (row g: its n_rows[g] proposals, then padding), logits [G, Lm, V], seq_index [G]: which
+        sequence (stream, cursors) each row belongs to -> (row dicts, committed lists, redraft lists [n_rows[g]], valid from
+        n_committed), one of each per row."""
+        G, Lm = int(proposed.shape[0]), int(proposed.shape[1])
+        if logits.dim() != 3 or logits.shape[0] != G or logits.shape[1] != Lm:
+            raise ValueError(f"forward must return logits [{G}, {Lm}, vocab], got {tuple(logits.shape)}")          # JDO:392-393
+        if G > self.max_rows or Lm > self.max_L or len(n_rows) != G or len(seq_index) != G:
+            raise RuntimeError("OnPolicyBatchStepper capacity exceeded")
+        if any(not 1 <= int(r) <= Lm for r in n_rows) or len(set(seq_index)) != G or any(not 0 <= int(i) < self.max_rows for i in seq_index):
+            raise ValueError("OnPolicyBatchStepper: row counts must lie in 1..Lm and the sequence indices must be distinct")
+        dev = self.device
+        V = int(logits.shape[-1])
+        n = G * Lm
+        flat = logits.reshape(n, V)
+        if flat.stride(1) != 1:
+            flat = flat.contiguous()
+        stride = flat.stride(0) if n > 1 else V
+        prop = proposed.to(device=dev, dtype=torch.int64).contiguous()
+        nr = torch.tensor([int(r) for r in n_rows], dtype=torch.int32).to(dev, non_blocking=True)
+        lib = N.lib()
+        self.ws = _grown(self.ws, int(lib.jf_rs_workspace_bytes(n, V)))
+        N.check(lib.jf_rs_probs(_ptr(flat), _dtype_code(flat), n, V, stride, _ptr(prop), float(temperature), _ptr(self.p_draft),
+                                _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed), _ptr(self.ws), self.ws.numel() * 4,
+                                _stream(dev)), "jf_rs_probs")
+        filt = None
+        if int(top_k) > 0 or float(top_p) > 0.0:
+            if self.filter is None:
+                self.filter = RowFilter(dev)
+            filt = self.filter.run(flat, prop.view(-1), temperature, top_k, top_p, self.p_draft, self.row_max, self.row_sumexp)
+        whole = [int(i) for i in seq_index] == list(range(G))      # the first G sequences in order: their slices are the arrays
+        if whole:
+            off, ln, cur = self.stream_off[:G], self.stream_len[:G], self.cursors[:G]
+        else:
+            idx = torch.tensor([int(i) for i in seq_index], dtype=torch.int64).to(dev, non_blocking=True)
+            off, ln, cur = self.stream_off.index_select(0, idx), self.stream_len.index_select(0, idx), self.cursors.index_select(0, idx)
+        cm, rd, rows = self.out[:n], self.out[n:2 * n], self.out[2 * n:2 * n + G * (N.OP_ROW_INTS // 2)]
+        N.check(lib.jf_rs_onpolicy_step_batch(_ptr(flat), _dtype_code(flat), V, stride, _ptr(prop), _ptr(nr), G, Lm,
+                                              _ptr(self.p_draft), _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed),
+                                              float(temperature), _ptr(self.stop_ids), int(self.stop_ids.numel()),
+                                              _ptr(self.u_stream), _ptr(self.m_stream), _ptr(off), _ptr(ln), _ptr(cur),
+                                              _ptr(cm), _ptr(rd), _ptr(rows), _ptr(self.step_ws), self.step_ws.numel() * 8,
+                                              _ptr(filt), _stream(dev)), "jf_rs_onpolicy_step_batch")
+        if not whole:
+            self.cursors.index_copy_(0, idx, cur)
+        end = 2 * n + G * (N.OP_ROW_INTS // 2)
+        self.out_host[:end].copy_(self.out[:end], non_blocking=True)
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()
+        host = self.out_host[:end].numpy()
+        recs = host[2 * n:end].view(np.int32).reshape(G, N.OP_ROW_INTS)
+        out_rows, out_cm, out_rd = [], [], []
+        for g in range(G):
+            row = dict(zip(N.OP_FIELDS, (int(x) for x in recs[g])))
+            if row["n_committed"] < 0:
+                raise RuntimeError(f"jf_rs_onpolicy_step_batch refused row {g} (row count or stream slice out of range)")
+            out_rows.append(row)
+            out_cm.append(host[g * Lm:g * Lm + row["n_committed"]].tolist())
+            out_rd.append(host[n + g * Lm:n + g * Lm + int(n_rows[g])].tolist())
+        return out_rows, out_cm, out_rd
