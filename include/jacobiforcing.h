@@ -612,7 +612,7 @@ JF_API int jf_rs_onpolicy_step(const void *logits, int dtype, int64_t V, int64_t
  * Every sequence has its own randomness: its uniforms are u_stream[stream_off[g][0] .. + stream_len[g][0]), its multinomial
  * draws m_stream[stream_off[g][1] .. + stream_len[g][1]), consumed cyclically from cursors[g][0] / cursors[g][1], which are
  * advanced.  Per sequence every decision, committed[g][..], redraft[g][..] and rows[g] are what jf_rs_onpolicy_step gives
- * for that sequence alone.  n_rows, stream_off and stream_len are device arrays: a sequence whose row count is outside
+ * for that sequence alone: both entry points launch the same kernels, jf_rs_onpolicy_step as G = 1, Lm = R.  n_rows, stream_off and stream_len are device arrays: a sequence whose row count is outside
  * 1..Lm, or whose slice is empty, gets rows[g].n_committed = -1 and nothing else of it is touched.
  */
 JF_API int jf_rs_onpolicy_step_batch(const void *logits, int dtype, int64_t V, int64_t row_stride, const int64_t *proposed /* [G, Lm] */,

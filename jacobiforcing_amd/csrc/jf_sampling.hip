@@ -4069,235 +4069,71 @@ __global__ __launch_bounds__(256, 4) void rs_step_fused_kernel(RsFusedArgs a) { 
 
 // ------------------------------------------------------------------------------------------------
 // On-policy rollout step (JDO = inference_engine/engine/jacobi_decoding_nongreedy_on_policy.py): sequential accept /
-// reject of ONE sequence's proposed tokens with a stop-token SET (JDO:270-327), then a fresh sample of every not yet
+// reject of a sequence's proposed tokens with a stop-token SET (JDO:270-327), then a fresh sample of every not yet
 // accepted position from this forward's distribution (JDO:465-477).
-//   rs_op_accept_kernel   one workgroup: the R accept tests are one ballot of its first wavefront (probabilities as in
-//                         rs_accept_entry; an undecided test is resolved with the row's float64 sum by the workgroup)
+//   rs_op_accept_kernel   one workgroup per sequence: its accept tests are ballots of the first wavefront (probabilities
+//                         as in rs_accept_entry; an undecided test is resolved with the row's float64 sum by the workgroup)
 //   rs_rowsum_a/b         float64 sums and exact CDF sums of the rejected row (+ its proposed token's interval) and of every
-//                         row after it (the re-draft candidates)
-//   rs_op_bonus_kernel    one workgroup: draws counted against the interval, ONE walk, stop flag, stream cursors
-//   rs_op_redraft_kernel  one workgroup per re-drafted row: one draw each; re-zeroes packed
+//                         row after it (the re-draft candidates); sel_row = -1 for everything that needs no sum
+//   rs_op_bonus_kernel    one workgroup per sequence: draws counted against the interval, ONE walk, stop flag, stream cursors
+//   rs_op_redraft_kernel  one workgroup per row: one draw for each re-drafted row; re-zeroes packed
+// The sequence dimension: the rows are a rectangle [G, Lm], flat row g * Lm + t, of which sequence g uses the first R_g; every
+// sequence has its own window of the two streams and its own two cursors (RsOpSeqs -> rs_op_seq).  Five launches whatever G
+// is.  jf_rs_onpolicy_step is G = 1, Lm = R with its scalar arguments; jf_rs_onpolicy_step_batch reads the per-sequence
+// values from device arrays, so there a sequence whose row count is outside 1..Lm (or whose stream window is empty) is found
+// by the accept launch: it gets n_committed = -1 and nothing else of it is touched.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool op_is_stop(const int32_t *stop_ids, int n_stop, int64_t tok) {
     for (int k = 0; k < n_stop; ++k) if (tok == (int64_t)stop_ids[k]) return true;
     return false;
 }
 
-constexpr int RS_OP_STAGE = 2048;
-template <int DT>
-__global__ __launch_bounds__(256) void rs_op_accept_kernel(RsAcceptIn in, const int64_t *proposed, int R,
-                                                            const int32_t *stop_ids, int n_stop, const float *u_stream,
-                                                            int64_t u_len, const int64_t *u_cursor, int64_t *committed,
-                                                            jf_op_row *out, RsWs w) {
-    __shared__ uint32_t s_p[RS_OP_STAGE];
-    __shared__ double s_tab[64], s_red[4];
-    __shared__ int s_unc, s_n, s_stop, s_rej, s_used;
-    uint32_t *g_patch = (uint32_t *)w.wtsum;      // !staged: one word per test, RS_PATCH_NONE = not resolved (the later launches overwrite it)
-    const int tid = threadIdx.x;
-    const int64_t uc = *u_cursor;
-    const bool staged = R <= RS_OP_STAGE;
-    rs_load_tab(s_tab);
-    if (staged) for (int i = tid; i < R; i += 256) s_p[i] = rs_accept_entry<DT>(in, i, proposed[i], -1, s_tab);
-    else for (int i = tid; i < R; i += 256) __hip_atomic_store(g_patch + i, RS_PATCH_NONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    for (;;) {
-        if (tid < 64) {
-            const int lane = tid;
-            int n = 0, stop = 0, rej = -1, used = 0, unc_at = -1;
-            for (int t0 = 0; t0 < R; t0 += 64) {                              // JDO:293-320
-                const int t = t0 + lane;
-                bool st = false, rejb = false, unc = false;
-                if (t < R) {
-                    uint32_t pe;
-                    if (staged) pe = s_p[t];
-                    else {
-                        pe = rs_accept_entry<DT>(in, t, proposed[t], -1, s_tab);
-                        const uint32_t q = __hip_atomic_load(g_patch + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (q != RS_PATCH_NONE) pe = q;
-                    }
-                    const float uu = u_stream[(uc + t) % u_len];
-                    rejb = !(uu < __uint_as_float(pe & RS_PE_VAL));
-                    unc = rejb && (pe & RS_PE_AMB) && uu < rs_accept_hi<DT>(pe);
-                    st = rejb || op_is_stop(stop_ids, n_stop, proposed[t]);
-                }
-                const unsigned long long bal = __ballot(st);
-                if (bal) {
-                    const int f = __builtin_ctzll(bal);
-                    if ((__ballot(unc) >> f) & 1ull) { unc_at = t0 + f; break; }
-                    const bool is_rej = (__ballot(rejb) >> f) & 1ull;
-                    if (is_rej) { rej = t0 + f; n = t0 + f; } else { stop = 1; n = t0 + f + 1; }
-                    used = t0 + f + 1;
-                    break;
-                }
-                const int wd = (R - t0) < 64 ? (R - t0) : 64;
-                n = t0 + wd; used = t0 + wd;
-            }
-            if (lane == 0) { s_unc = unc_at; s_n = n; s_stop = stop; s_rej = rej; s_used = used; }
-        }
-        __syncthreads();
-        const int ui = s_unc;
-        if (ui < 0) break;
-        const float pex = rs_exact_prob_wg<DT>(in.logits, ui, in.V, in.row_stride, in.t, in.row_max[ui], proposed[ui], s_tab, s_red);
-        if (tid == 0) {
-            const uint32_t word = __float_as_uint(pex > 1.f ? 1.f : pex) & RS_PE_VAL;
-            if (staged) s_p[ui] = word;
-            else __hip_atomic_store(g_patch + ui, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-    }
-    const int n = s_n, rej = s_rej;
-    for (int i = tid; i < n; i += 256) committed[i] = proposed[i];
-    for (int i = tid; i < R; i += 256) {
-        w.sel_row[i] = (rej >= 0 && i >= rej) ? i : -1;
-        w.avoid[i] = (i == rej) ? (int32_t)proposed[i] : -1;
-    }
-    if (tid == 0) {
-        out->n_committed = n; out->stop_hit = s_stop; out->reject_pos = rej; out->n_bonus_draws = 0;
-        out->n_uniforms = s_used; out->n_redraft = 0; out->redraft_base_lo = 0; out->redraft_base_hi = 0;
-    }
-}
-
-template <int DT>
-__global__ __launch_bounds__(256) void rs_op_bonus_kernel(const void *logits, int64_t V, int64_t row_stride, const int64_t *proposed,
-                                                           int R, const float *row_max, const float *row_sumexp, float temp,
-                                                           const int32_t *stop_ids, int n_stop, int64_t *u_cursor,
-                                                           const float *m_stream, int64_t m_len, int64_t *m_cursor,
-                                                           int64_t *committed, jf_op_row *out, RsWs w) {
-    __shared__ RsPickShared sh;
-    __shared__ float s_uf;
-    __shared__ int s_draws;
-    const int tid = threadIdx.x;
-    const int rej = out->reject_pos;
-    const int64_t mc = *m_cursor;
-    int n = out->n_committed, stop = out->stop_hit, draws = 0;
-    rs_load_tab(sh.tab);
-    if (rej >= 0) {                                                    // JDO:157-168 (bonus != proposed)
-        if (tid < 64) {
-            double t_, lo_, hi_;
-            rs_interval(w, rej, V, Elem<DT>::EPV, t_, lo_, hi_);
-            float uf;
-            const int d = rs_count_draws([&](int tr) { return m_stream[(mc + tr) % m_len]; }, t_, lo_, hi_, tid, &uf);
-            if (tid == 0) { s_uf = uf; s_draws = d; }
-        }
-        __syncthreads();
-        draws = s_draws;
-        const RsRow row = rs_step_row<DT>(logits, rej, V, row_stride, temp, row_max, row_sumexp, w.filt);
-        const int bonus = rs_final_pick<DT, false>(row, w, rej, w.s64[rej], proposed[rej], s_uf, sh);
-        if (tid == 0) committed[n] = bonus;
-        n += 1;
-        if (op_is_stop(stop_ids, n_stop, bonus)) stop = 1;
-    }
-    if (tid == 0) {
-        const int n_redraft = (!stop && n < R) ? R - n : 0;            // JDO:465: not stopped and accepted < gen_len
-        const int64_t base = mc + draws;
-        out->n_committed = n; out->stop_hit = stop; out->n_bonus_draws = draws; out->n_redraft = n_redraft;
-        out->redraft_base_lo = (int32_t)(base & 0xFFFFFFFFll); out->redraft_base_hi = (int32_t)(base >> 32);
-        *u_cursor += out->n_uniforms;
-        *m_cursor = base + n_redraft;
-    }
-}
-
-// one workgroup per logits row: rows >= n_committed draw one sample each; every row's argmax slot is re-zeroed.
-template <int DT>
-__global__ __launch_bounds__(256) void rs_op_redraft_kernel(const void *logits, int64_t V, int64_t row_stride, int R,
-                                                             const float *row_max, const float *row_sumexp, float temp,
-                                                             const float *m_stream, int64_t m_len, const jf_op_row *res,
-                                                             RsWs w, int64_t *redraft, unsigned long long *packed) {
-    __shared__ RsPickShared sh;
-    const int li = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) packed[li] = 0ull;
-    const int n = res->n_committed;
-    if (res->n_redraft <= 0 || li < n) return;
-    rs_load_tab(sh.tab);
-    __syncthreads();
-    const int64_t base = ((int64_t)res->redraft_base_hi << 32) | (int64_t)(uint32_t)res->redraft_base_lo;
-    const RsRow row = rs_step_row<DT>(logits, li, V, row_stride, temp, row_max, row_sumexp, w.filt);
-    const float u = m_stream[(base + (li - n)) % m_len];
-    int y;
-    if (rs_hier_ok(V, Elem<DT>::EPV)) {
-        if (tid < 64) { const int yy = rs_pick_wave<DT, false>(row, w, li, w.s64[li], u, sh.tab, tid); if (tid == 0) sh.pick = yy; }
-        __syncthreads();
-        y = sh.pick;
-    } else {
-        y = rs_pick_wg<DT>(row, w.segsum + (int64_t)li * RS_SEG, w.s64[li], u, sh);
-    }
-    if (tid == 0) redraft[li] = y;
-}
-
-extern "C" int jf_rs_onpolicy_step(const void *logits, int dtype, int64_t V, int64_t row_stride, const int64_t *proposed, int R,
-                                   const float *p_draft, const float *row_max, const float *row_sumexp, uint64_t *packed,
-                                   float temperature, const int32_t *stop_ids, int n_stop, const float *u_stream, int64_t u_len,
-                                   int64_t *u_cursor, const float *m_stream, int64_t m_len, int64_t *m_cursor,
-                                   int64_t *committed, int64_t *redraft, jf_op_row *row, void *workspace,
-                                   size_t workspace_bytes, const jf_rs_filter_row *filt, void *stream) {
-    if (R <= 0) return JF_OK;
-    if (!logits || !proposed || !p_draft || !row_max || !row_sumexp || !packed || !u_stream || !u_cursor || !m_stream ||
-        !m_cursor || !committed || !redraft || !row || !workspace || (n_stop > 0 && !stop_ids))
-        return fail(JF_E_INVALID, "jf_rs_onpolicy_step: null pointer");
-    if (u_len <= 0 || m_len <= 0 || n_stop < 0) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: empty random stream");
-    if (workspace_bytes < rs_ws_bytes(R) || ((uintptr_t)workspace % 16) != 0) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: workspace too small or not 16-byte aligned");
-    if (dtype != JF_F32 && dtype != JF_BF16) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: dtype %d", dtype);
-    if (V <= 0 || V > 0x7FFFFFFFll) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: V=%lld", (long long)V);
-    float t = (temperature <= 0.f) ? 1.f : temperature;
-    if (dtype == JF_BF16 && t != 1.f && rs_scale_is_exact(t)) t = -t;    // the kernels' rows take the product form of the scaling (rs_make_row)
-    hipStream_t s = (hipStream_t)stream;
-    RsWs w = rs_ws(workspace, R);
-    w.filt = filt;
-    unsigned long long *pk = (unsigned long long *)packed;
-    const RsAcceptIn in{logits, V, row_stride, t, row_max, row_sumexp, p_draft};
-#define JF_OP(DT)                                                                                                                              \
-    rs_op_accept_kernel<DT><<<1, 256, 0, s>>>(in, proposed, R, stop_ids, n_stop, u_stream, u_len, u_cursor, committed, row, w);                 \
-    rs_rowsum_a_kernel<DT><<<R * RS_SEG, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                                        \
-    rs_rowsum_b_kernel<DT><<<R * RS_SEG, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                                        \
-    rs_op_bonus_kernel<DT><<<1, 256, 0, s>>>(logits, V, row_stride, proposed, R, row_max, row_sumexp, t, stop_ids, n_stop, u_cursor, m_stream,  \
-                                             m_len, m_cursor, committed, row, w);                                                               \
-    rs_op_redraft_kernel<DT><<<R, 256, 0, s>>>(logits, V, row_stride, R, row_max, row_sumexp, t, m_stream, m_len, row, w, redraft, pk)
-    if (dtype == JF_F32) { JF_OP(JF_F32); } else { JF_OP(JF_BF16); }
-#undef JF_OP
-    return check_launch("rs_onpolicy kernels");
-}
-
-// ------------------------------------------------------------------------------------------------
-// The on-policy step of G sequences in one call (lock-step rollouts): the rows are a rectangle [G, Lm], flat row g * Lm + t,
-// of which sequence g uses the first n_rows[g]; every sequence has its own slice of the two streams and its own two cursors.
-// The decisions are rs_op_*'s, written with the sequence dimension: the accept walk and the bonus walk take one workgroup
-// per sequence, the row sums cover G * Lm items (sel_row = -1 for everything that needs no sum, the padded tail included),
-// the re-draft launch maps a flat row to (g, t).  Five launches whatever G is.  A sequence whose n_rows is outside 1..Lm
-// (or whose stream slice is empty) gets n_committed = -1 and nothing else of it is touched.
-// ------------------------------------------------------------------------------------------------
-struct RsOpbSeq {                   // what the launches of the batch step know about the sequences
-    const int32_t *n_rows;          // [G]
-    const int64_t *stream_off, *stream_len;   // [G, 2] uniforms / multinomial
-    int64_t *cursors;               // [G, 2]
+struct RsOpSeqs {                   // the sequences of one call, by value
+    const int32_t *n_rows;          // [G] rows per sequence; null: ONE sequence of Lm rows whose streams are u_len / m_len long
+    const int64_t *stream_off, *stream_len;   // [G, 2] uniforms / multinomial (with n_rows)
+    int64_t u_len, m_len;           // (without n_rows)
+    const float *u_stream, *m_stream;
+    int64_t *u_cursor, *m_cursor;   // sequence g's cursors are u_cursor[2 * g] and m_cursor[2 * g]
     int Lm;
 };
-__device__ __forceinline__ bool opb_valid(const RsOpbSeq &q, int g) {
+struct RsOpSeq {                    // sequence g of them
+    int R;
+    const float *u_stream, *m_stream;
+    int64_t u_len, m_len;
+    int64_t *u_cursor, *m_cursor;
+    bool valid;
+};
+__device__ __forceinline__ RsOpSeq rs_op_seq(const RsOpSeqs &q, int g) {
+    if (!q.n_rows) return {q.Lm, q.u_stream, q.m_stream, q.u_len, q.m_len, q.u_cursor, q.m_cursor, true};   // the host has checked it
     const int R = q.n_rows[g];
-    return R >= 1 && R <= q.Lm && q.stream_len[2 * g] > 0 && q.stream_len[2 * g + 1] > 0 && q.stream_off[2 * g] >= 0 &&
-           q.stream_off[2 * g + 1] >= 0;
+    const int64_t uo = q.stream_off[2 * g], mo = q.stream_off[2 * g + 1], ul = q.stream_len[2 * g], ml = q.stream_len[2 * g + 1];
+    return {R, q.u_stream + uo, q.m_stream + mo, ul, ml, q.u_cursor + 2 * g, q.m_cursor + 2 * g,
+            R >= 1 && R <= q.Lm && ul > 0 && ml > 0 && uo >= 0 && mo >= 0};
 }
 
+constexpr int RS_OP_STAGE = 2048;
 template <int DT>
-__global__ __launch_bounds__(256) void rs_opb_accept_kernel(RsAcceptIn in, const int64_t *proposed_all, RsOpbSeq q,
-                                                             const int32_t *stop_ids, int n_stop, const float *u_all,
-                                                             int64_t *committed_all, jf_op_row *rows, RsWs w) {
+__global__ __launch_bounds__(256) void rs_op_accept_kernel(RsAcceptIn in, const int64_t *proposed_all, RsOpSeqs q,
+                                                            const int32_t *stop_ids, int n_stop, int64_t *committed_all,
+                                                            jf_op_row *rows, RsWs w) {
     __shared__ uint32_t s_p[RS_OP_STAGE];
     __shared__ double s_tab[64], s_red[4];
     __shared__ int s_unc, s_n, s_stop, s_rej, s_used;
     const int g = blockIdx.x, tid = threadIdx.x, Lm = q.Lm;
     const int64_t base = (int64_t)g * Lm;                     // the sequence's first flat row
     jf_op_row *out = rows + g;
-    if (!opb_valid(q, g)) {                                    // workgroup-uniform
+    const RsOpSeq sq = rs_op_seq(q, g);
+    if (!sq.valid) {                                           // workgroup-uniform
         for (int i = tid; i < Lm; i += 256) { w.sel_row[base + i] = -1; w.avoid[base + i] = -1; }
         if (tid == 0) out->n_committed = -1;
         return;
     }
-    const int R = q.n_rows[g];
+    const int R = sq.R;
     const int64_t *proposed = proposed_all + base;
     int64_t *committed = committed_all + base;
-    const float *u_stream = u_all + q.stream_off[2 * g];
-    const int64_t u_len = q.stream_len[2 * g], uc = q.cursors[2 * g];
-    uint32_t *g_patch = (uint32_t *)w.wtsum + base;           // !staged: one word per test of this sequence (rs_op_accept_kernel)
+    const float *u_stream = sq.u_stream;
+    const int64_t u_len = sq.u_len, uc = *sq.u_cursor;
+    uint32_t *g_patch = (uint32_t *)w.wtsum + base;           // !staged: one word per test, RS_PATCH_NONE = not resolved (the later launches overwrite it)
     const bool staged = R <= RS_OP_STAGE;
     rs_load_tab(s_tab);
     if (staged) for (int i = tid; i < R; i += 256) s_p[i] = rs_accept_entry<DT>(in, base + i, proposed[i], -1, s_tab);
@@ -4361,10 +4197,10 @@ __global__ __launch_bounds__(256) void rs_opb_accept_kernel(RsAcceptIn in, const
 }
 
 template <int DT>
-__global__ __launch_bounds__(256) void rs_opb_bonus_kernel(const void *logits, int64_t V, int64_t row_stride, const int64_t *proposed_all,
-                                                            RsOpbSeq q, const float *row_max, const float *row_sumexp, float temp,
-                                                            const int32_t *stop_ids, int n_stop, const float *m_all,
-                                                            int64_t *committed_all, jf_op_row *rows, RsWs w) {
+__global__ __launch_bounds__(256) void rs_op_bonus_kernel(const void *logits, int64_t V, int64_t row_stride, const int64_t *proposed_all,
+                                                           RsOpSeqs q, const float *row_max, const float *row_sumexp, float temp,
+                                                           const int32_t *stop_ids, int n_stop, int64_t *committed_all,
+                                                           jf_op_row *rows, RsWs w) {
     __shared__ RsPickShared sh;
     __shared__ float s_uf;
     __shared__ int s_draws;
@@ -4372,10 +4208,11 @@ __global__ __launch_bounds__(256) void rs_opb_bonus_kernel(const void *logits, i
     jf_op_row *out = rows + g;
     if (out->n_committed < 0) return;                          // the accept launch refused the sequence (workgroup-uniform)
     const int64_t base = (int64_t)g * q.Lm;
-    const int R = q.n_rows[g];
+    const RsOpSeq sq = rs_op_seq(q, g);
+    const int R = sq.R;
     const int64_t *proposed = proposed_all + base;
-    const float *m_stream = m_all + q.stream_off[2 * g + 1];
-    const int64_t m_len = q.stream_len[2 * g + 1], mc = q.cursors[2 * g + 1];
+    const float *m_stream = sq.m_stream;
+    const int64_t m_len = sq.m_len, mc = *sq.m_cursor;
     const int rej = out->reject_pos;
     int n = out->n_committed, stop = out->stop_hit, draws = 0;
     rs_load_tab(sh.tab);
@@ -4401,31 +4238,31 @@ __global__ __launch_bounds__(256) void rs_opb_bonus_kernel(const void *logits, i
         const int64_t mbase = mc + draws;
         out->n_committed = n; out->stop_hit = stop; out->n_bonus_draws = draws; out->n_redraft = n_redraft;
         out->redraft_base_lo = (int32_t)(mbase & 0xFFFFFFFFll); out->redraft_base_hi = (int32_t)(mbase >> 32);
-        q.cursors[2 * g] += out->n_uniforms;
-        q.cursors[2 * g + 1] = mbase + n_redraft;
+        *sq.u_cursor += out->n_uniforms;
+        *sq.m_cursor = mbase + n_redraft;
     }
 }
 
-// one workgroup per flat row (g, t): rows n_committed <= t < n_rows[g] draw one sample each; every row's argmax slot is re-zeroed.
+// one workgroup per flat row (g, t): rows n_committed <= t < R_g draw one sample each; every row's argmax slot is re-zeroed.
 template <int DT>
-__global__ __launch_bounds__(256) void rs_opb_redraft_kernel(const void *logits, int64_t V, int64_t row_stride, RsOpbSeq q,
-                                                              const float *row_max, const float *row_sumexp, float temp,
-                                                              const float *m_all, const jf_op_row *rows, RsWs w,
-                                                              int64_t *redraft, unsigned long long *packed) {
+__global__ __launch_bounds__(256) void rs_op_redraft_kernel(const void *logits, int64_t V, int64_t row_stride, RsOpSeqs q,
+                                                             const float *row_max, const float *row_sumexp, float temp,
+                                                             const jf_op_row *rows, RsWs w, int64_t *redraft,
+                                                             unsigned long long *packed) {
     __shared__ RsPickShared sh;
     const int li = blockIdx.x, tid = threadIdx.x;
     const int g = li / q.Lm, t = li % q.Lm;
     if (tid == 0) packed[li] = 0ull;
     const jf_op_row *res = rows + g;
     const int n = res->n_committed;
-    if (n < 0 || res->n_redraft <= 0 || t < n || t >= q.n_rows[g]) return;
-    const float *m_stream = m_all + q.stream_off[2 * g + 1];
-    const int64_t m_len = q.stream_len[2 * g + 1];
+    if (n < 0 || res->n_redraft <= 0 || t < n) return;
+    const RsOpSeq sq = rs_op_seq(q, g);
+    if (t >= sq.R) return;
     rs_load_tab(sh.tab);
     __syncthreads();
     const int64_t mbase = ((int64_t)res->redraft_base_hi << 32) | (int64_t)(uint32_t)res->redraft_base_lo;
     const RsRow row = rs_step_row<DT>(logits, li, V, row_stride, temp, row_max, row_sumexp, w.filt);
-    const float u = m_stream[(mbase + (t - n)) % m_len];
+    const float u = sq.m_stream[(mbase + (t - n)) % sq.m_len];
     int y;
     if (rs_hier_ok(V, Elem<DT>::EPV)) {
         if (tid < 64) { const int yy = rs_pick_wave<DT, false>(row, w, li, w.s64[li], u, sh.tab, tid); if (tid == 0) sh.pick = yy; }
@@ -4435,6 +4272,50 @@ __global__ __launch_bounds__(256) void rs_opb_redraft_kernel(const void *logits,
         y = rs_pick_wg<DT>(row, w.segsum + (int64_t)li * RS_SEG, w.s64[li], u, sh);
     }
     if (tid == 0) redraft[li] = y;
+}
+
+// the five launches of both entry points: G sequences of up to q.Lm rows each (the caller has validated everything host-visible)
+static int rs_op_launch(const void *logits, int dtype, int64_t V, int64_t row_stride, const int64_t *proposed, int G,
+                        const RsOpSeqs &q, const float *p_draft, const float *row_max, const float *row_sumexp, uint64_t *packed,
+                        float temperature, const int32_t *stop_ids, int n_stop, int64_t *committed, int64_t *redraft,
+                        jf_op_row *rows, void *workspace, const jf_rs_filter_row *filt, void *stream, const char *what) {
+    float t = (temperature <= 0.f) ? 1.f : temperature;
+    if (dtype == JF_BF16 && t != 1.f && rs_scale_is_exact(t)) t = -t;    // the kernels' rows take the product form of the scaling (rs_make_row)
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = (int64_t)G * q.Lm;
+    RsWs w = rs_ws(workspace, N);
+    w.filt = filt;
+    unsigned long long *pk = (unsigned long long *)packed;
+    const RsAcceptIn in{logits, V, row_stride, t, row_max, row_sumexp, p_draft};
+    const unsigned nseg = (unsigned)(N * RS_SEG), nrow = (unsigned)N;
+#define JF_OP(DT)                                                                                                                              \
+    rs_op_accept_kernel<DT><<<G, 256, 0, s>>>(in, proposed, q, stop_ids, n_stop, committed, rows, w);                                           \
+    rs_rowsum_a_kernel<DT><<<nseg, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                                              \
+    rs_rowsum_b_kernel<DT><<<nseg, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                                              \
+    rs_op_bonus_kernel<DT><<<G, 256, 0, s>>>(logits, V, row_stride, proposed, q, row_max, row_sumexp, t, stop_ids, n_stop, committed, rows, w); \
+    rs_op_redraft_kernel<DT><<<nrow, 256, 0, s>>>(logits, V, row_stride, q, row_max, row_sumexp, t, rows, w, redraft, pk)
+    if (dtype == JF_F32) { JF_OP(JF_F32); } else { JF_OP(JF_BF16); }
+#undef JF_OP
+    return check_launch(what);
+}
+
+extern "C" int jf_rs_onpolicy_step(const void *logits, int dtype, int64_t V, int64_t row_stride, const int64_t *proposed, int R,
+                                   const float *p_draft, const float *row_max, const float *row_sumexp, uint64_t *packed,
+                                   float temperature, const int32_t *stop_ids, int n_stop, const float *u_stream, int64_t u_len,
+                                   int64_t *u_cursor, const float *m_stream, int64_t m_len, int64_t *m_cursor,
+                                   int64_t *committed, int64_t *redraft, jf_op_row *row, void *workspace,
+                                   size_t workspace_bytes, const jf_rs_filter_row *filt, void *stream) {
+    if (R <= 0) return JF_OK;
+    if (!logits || !proposed || !p_draft || !row_max || !row_sumexp || !packed || !u_stream || !u_cursor || !m_stream ||
+        !m_cursor || !committed || !redraft || !row || !workspace || (n_stop > 0 && !stop_ids))
+        return fail(JF_E_INVALID, "jf_rs_onpolicy_step: null pointer");
+    if (u_len <= 0 || m_len <= 0 || n_stop < 0) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: empty random stream");
+    if (workspace_bytes < rs_ws_bytes(R) || ((uintptr_t)workspace % 16) != 0) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: workspace too small or not 16-byte aligned");
+    if (dtype != JF_F32 && dtype != JF_BF16) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: dtype %d", dtype);
+    if (V <= 0 || V > 0x7FFFFFFFll) return fail(JF_E_INVALID, "jf_rs_onpolicy_step: V=%lld", (long long)V);
+    const RsOpSeqs q{nullptr, nullptr, nullptr, u_len, m_len, u_stream, m_stream, u_cursor, m_cursor, R};   // one sequence of R rows
+    return rs_op_launch(logits, dtype, V, row_stride, proposed, 1, q, p_draft, row_max, row_sumexp, packed, temperature, stop_ids,
+                        n_stop, committed, redraft, row, workspace, filt, stream, "rs_onpolicy kernels");
 }
 
 extern "C" int jf_rs_onpolicy_step_batch(const void *logits, int dtype, int64_t V, int64_t row_stride, const int64_t *proposed,
@@ -4454,25 +4335,9 @@ extern "C" int jf_rs_onpolicy_step_batch(const void *logits, int dtype, int64_t 
     if (workspace_bytes < rs_ws_bytes(N) || ((uintptr_t)workspace % 16) != 0) return fail(JF_E_INVALID, "jf_rs_onpolicy_step_batch: workspace too small or not 16-byte aligned");
     if (dtype != JF_F32 && dtype != JF_BF16) return fail(JF_E_INVALID, "jf_rs_onpolicy_step_batch: dtype %d", dtype);
     if (V <= 0 || V > 0x7FFFFFFFll) return fail(JF_E_INVALID, "jf_rs_onpolicy_step_batch: V=%lld", (long long)V);
-    float t = (temperature <= 0.f) ? 1.f : temperature;
-    if (dtype == JF_BF16 && t != 1.f && rs_scale_is_exact(t)) t = -t;    // the kernels' rows take the product form of the scaling (rs_make_row)
-    hipStream_t s = (hipStream_t)stream;
-    RsWs w = rs_ws(workspace, N);
-    w.filt = filt;
-    unsigned long long *pk = (unsigned long long *)packed;
-    const RsAcceptIn in{logits, V, row_stride, t, row_max, row_sumexp, p_draft};
-    const RsOpbSeq q{n_rows, stream_off, stream_len, cursors, Lm};
-    const unsigned nseg = (unsigned)(N * RS_SEG), nrow = (unsigned)N;
-#define JF_OPB(DT)                                                                                                                             \
-    rs_opb_accept_kernel<DT><<<G, 256, 0, s>>>(in, proposed, q, stop_ids, n_stop, u_stream, committed, rows, w);                                \
-    rs_rowsum_a_kernel<DT><<<nseg, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                                              \
-    rs_rowsum_b_kernel<DT><<<nseg, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                                              \
-    rs_opb_bonus_kernel<DT><<<G, 256, 0, s>>>(logits, V, row_stride, proposed, q, row_max, row_sumexp, t, stop_ids, n_stop, m_stream,           \
-                                              committed, rows, w);                                                                              \
-    rs_opb_redraft_kernel<DT><<<nrow, 256, 0, s>>>(logits, V, row_stride, q, row_max, row_sumexp, t, m_stream, rows, w, redraft, pk)
-    if (dtype == JF_F32) { JF_OPB(JF_F32); } else { JF_OPB(JF_BF16); }
-#undef JF_OPB
-    return check_launch("rs_onpolicy batch kernels");
+    const RsOpSeqs q{n_rows, stream_off, stream_len, 0, 0, u_stream, m_stream, cursors, cursors + 1, Lm};
+    return rs_op_launch(logits, dtype, V, row_stride, proposed, G, q, p_draft, row_max, row_sumexp, packed, temperature, stop_ids,
+                        n_stop, committed, redraft, rows, workspace, filt, stream, "rs_onpolicy batch kernels");
 }
 
 // May the one-launch step run on this device?  Its three role workgroups and the workgroups of two rows (a row's wait for each

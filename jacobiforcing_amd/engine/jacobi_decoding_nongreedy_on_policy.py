@@ -220,22 +220,65 @@ class JacobiDecoderNonGreedyOnPolicy:
             return [rnd.randrange(self.vocab_size) for _ in range(block_len)]
         return [rnd.choice(choices) for _ in range(block_len)]
 
+    def _sampling_of(self, seq: Sequence) -> Tuple[float, int, float]:
+        """(temperature, top_k, top_p); the filters are planted on the request object (JDO:132-133 reads them with getattr)."""
+        sp = getattr(seq, "sampling_params", None)
+        temperature = float(getattr(sp, "temperature", 1.0)) if sp is not None else 1.0
+        return (temperature,) + ops.active_filters(sp, self.vocab_size)
+
+    @staticmethod
+    def _check_vocab(proposed, V: int) -> None:
+        """JDO:298-301"""
+        bad = next((x for x in proposed if not 0 <= x < V), None)
+        if bad is not None:
+            raise ValueError(f"Token index {bad} out of bounds for vocab size {V}. "
+                             "This may indicate a mismatch between model vocab and tokenizer vocab.")
+
+    def _commit_row(self, seq: Sequence, blk: _BlockState, proposed: List[int], row: dict, committed: List[int],
+                    redraft: List[int], cursors: List[int], cached_positions: int, completion_start_len: int) -> int:
+        """What one step's record does to its sequence and block (JDO:412-477); ``cursors``: the [uniforms, multinomial] draw
+        counts to advance; ``cached_positions``: how many positions behind the seed the forward cached.  Returns the number
+        of tokens appended."""
+        bm = self.block_manager
+        cursors[0] += row["n_uniforms"]
+        cursors[1] += row["n_bonus_draws"] + row["n_redraft"]
+        stop_hit = bool(row["stop_hit"])
+        if not committed:
+            committed, stop_hit = [proposed[0]], proposed[0] in blk.stop
+        seq.extend_tokens(committed)                                                # JDO:412-416
+        if bm is not None:
+            bm.may_append_batch(seq, len(committed))
+            if cached_positions > len(committed):
+                bm.trim_kv_only_fast(seq, cached_positions - len(committed))        # JDO:420-426
+        seq.clear_draft()
+        if len(seq) != seq.num_cached_tokens:
+            raise RuntimeError(f"Invariant violated: len(token_ids)={len(seq)} != num_cached_tokens={seq.num_cached_tokens}")
+        first_new = blk.accept(committed)
+        if stop_hit:                                                                 # JDO:439-463
+            kept = _truncate_after_stop(list(seq.token_ids), completion_start_len, self.stop_token_ids)
+            dropped = len(seq.token_ids) - len(kept)
+            if dropped:
+                seq.token_ids = kept
+                if bm is not None:
+                    bm.trim_kv_only_fast(seq, dropped)
+            blk.close_at_stop(first_new)
+        elif blk.accepted < blk.gen_len:                                             # JDO:465-477 (samples drawn on the GPU)
+            blk.refill(redraft[len(committed):])
+        blk.snapshot()
+        return len(committed)
+
     # ------------------------------------------------------------------------------- one block (JDO:331-488)
     @torch.inference_mode()
-    def _run_one_block(self, seq: Sequence, block_len: int, token_budget_remaining: int, completion_start_len: int,
-                       profiler=None) -> Tuple[List[List[int]], int, int, bool]:
+    def _run_one_block(self, seq: Sequence, block_len: int, token_budget_remaining: int,
+                       completion_start_len: int) -> Tuple[List[List[int]], int, int, bool]:
         """Returns (trajectory, tokens appended, forwards used, stopped)."""
         if int(block_len) <= 0 or token_budget_remaining <= 0:
             return [], 0, 0, True
         blk = _BlockState(int(block_len), min(int(block_len), int(token_budget_remaining)), self.pad_token_id,
                           self.stop_token_ids)
         blk.start(self._init_block_draft_from_prompt(list(seq.token_ids), blk.gen_len))
-        sp = getattr(seq, "sampling_params", None)
-        temperature = float(getattr(sp, "temperature", 1.0)) if sp is not None else 1.0
-        top_k, top_p = ops.active_filters(sp, self.vocab_size)         # planted on the request object (JDO:132-133 reads them with getattr)
+        temperature, top_k, top_p = self._sampling_of(seq)
         st = self._ensure(blk.full_len + 1)
-        bm = self.block_manager
-        tick = (lambda name, on: (profiler.start(name) if on else profiler.stop(name))) if profiler else (lambda name, on: None)
         fwd_used = appended_total = 0
         while blk.open():
             if not seq.token_ids:
@@ -244,48 +287,14 @@ class JacobiDecoderNonGreedyOnPolicy:
             remaining = len(proposed)
             draft = torch.tensor([[int(seq.token_ids[-1])] + proposed], dtype=torch.long, device=self.device)
             seq.draft_tokens = draft[0].tolist()
-            tick("jacobi.forward", True)
             logits = self._forward_single(seq, draft)                               # [1, remaining, V]
             fwd_used += 1
-            tick("jacobi.forward", False)
             if logits.ndim != 3 or int(logits.size(0)) != 1 or int(logits.size(1)) != remaining:
                 raise ValueError(f"forward must return logits [1, {remaining}, vocab], got {tuple(logits.shape)}")
-            V = int(logits.size(-1))
-            bad = next((x for x in proposed if not 0 <= x < V), None)                # JDO:298-301
-            if bad is not None:
-                raise ValueError(f"Token index {bad} out of bounds for vocab size {V}. "
-                                 "This may indicate a mismatch between model vocab and tokenizer vocab.")
-            tick("jacobi.verify", True)
+            self._check_vocab(proposed, int(logits.size(-1)))
             row, committed, redraft = st.step(draft[0, 1:], logits[0], temperature, self._cur, top_k, top_p)
-            self._cur[0] += row["n_uniforms"]
-            self._cur[1] += row["n_bonus_draws"] + row["n_redraft"]
-            stop_hit = bool(row["stop_hit"])
-            tick("jacobi.verify", False)
-            if not committed:
-                committed, stop_hit = [proposed[0]], proposed[0] in blk.stop
-            tick("jacobi.commit", True)
-            seq.extend_tokens(committed)                                            # JDO:412-416
-            if bm is not None:
-                bm.may_append_batch(seq, len(committed))
-                if remaining > len(committed):
-                    bm.trim_kv_only_fast(seq, remaining - len(committed))           # JDO:420-426
-            tick("jacobi.commit", False)
-            appended_total += len(committed)
-            seq.clear_draft()
-            if len(seq) != seq.num_cached_tokens:
-                raise RuntimeError(f"Invariant violated: len(token_ids)={len(seq)} != num_cached_tokens={seq.num_cached_tokens}")
-            first_new = blk.accept(committed)
-            if stop_hit:                                                             # JDO:439-463
-                kept = _truncate_after_stop(list(seq.token_ids), completion_start_len, self.stop_token_ids)
-                dropped = len(seq.token_ids) - len(kept)
-                if dropped:
-                    seq.token_ids = kept
-                    if bm is not None:
-                        bm.trim_kv_only_fast(seq, dropped)
-                blk.close_at_stop(first_new)
-            elif blk.accepted < blk.gen_len:                                         # JDO:465-477 (samples drawn on the GPU)
-                blk.refill(redraft[len(committed):])
-            blk.snapshot()
+            appended_total += self._commit_row(seq, blk, proposed, row, committed, redraft, self._cur, remaining,
+                                               completion_start_len)
         return blk.trajectory, appended_total, fwd_used, blk.stopped
 
     # ------------------------------------------------------------------------------- one block round, all sequences together
@@ -294,9 +303,7 @@ class JacobiDecoderNonGreedyOnPolicy:
         padded length would push over ``max_forward_positions`` is stepped alone (its own forward fits, as it would today)."""
         by_key: Dict[tuple, List[int]] = {}
         for i in rows:
-            sp = getattr(seqs[i], "sampling_params", None)
-            temperature = float(getattr(sp, "temperature", 1.0)) if sp is not None else 1.0
-            by_key.setdefault((temperature,) + ops.active_filters(sp, self.vocab_size), []).append(i)
+            by_key.setdefault(self._sampling_of(seqs[i]), []).append(i)
         bound, groups = self.max_forward_positions, []
         for members in by_key.values():
             alone: List[int] = []
@@ -319,7 +326,7 @@ class JacobiDecoderNonGreedyOnPolicy:
             return {}
         st = self._ensure_batch(len(seqs), max(int(block_lens[i]) for i in rows) + 1)
         rnds = self._seq_streams[0]
-        bm, pad = self.block_manager, self.pad_token_id
+        pad = self.pad_token_id
         blocks: Dict[int, _BlockState] = {}
         fwd_used, appended = {i: 0 for i in rows}, {i: 0 for i in rows}
         for i in rows:                                                               # every block opens from the round's start state
@@ -346,44 +353,13 @@ class JacobiDecoderNonGreedyOnPolicy:
                 self.lockstep_forwards.append((len(group), Lm, sum(n_rows)))
                 if logits.ndim != 3 or int(logits.size(0)) != len(group) or int(logits.size(1)) != Lm:
                     raise ValueError(f"forward must return logits [{len(group)}, {Lm}, vocab], got {tuple(logits.shape)}")
-                V = int(logits.size(-1))
-                bad = next((x for p in proposed for x in p if not 0 <= x < V), None)   # JDO:298-301
-                if bad is not None:
-                    raise ValueError(f"Token index {bad} out of bounds for vocab size {V}. "
-                                     "This may indicate a mismatch between model vocab and tokenizer vocab.")
-                sp = getattr(gs[0], "sampling_params", None)
-                temperature = float(getattr(sp, "temperature", 1.0)) if sp is not None else 1.0
-                top_k, top_p = ops.active_filters(sp, self.vocab_size)
+                self._check_vocab((x for p in proposed for x in p), int(logits.size(-1)))
+                temperature, top_k, top_p = self._sampling_of(gs[0])
                 recs, committed_all, redraft_all = st.step(draft[:, 1:], n_rows, logits, temperature, group, top_k, top_p)
                 for i, seq, prop, row, committed, redraft in zip(group, gs, proposed, recs, committed_all, redraft_all):
-                    blk = blocks[i]
-                    self.cursors_per_sequence[i][0] += row["n_uniforms"]
-                    self.cursors_per_sequence[i][1] += row["n_bonus_draws"] + row["n_redraft"]
-                    stop_hit = bool(row["stop_hit"])
-                    if not committed:
-                        committed, stop_hit = [prop[0]], prop[0] in blk.stop
-                    seq.extend_tokens(committed)                                     # JDO:412-416
-                    if bm is not None:
-                        bm.may_append_batch(seq, len(committed))
-                        if Lm > len(committed):
-                            bm.trim_kv_only_fast(seq, Lm - len(committed))          # the forward cached Lm positions behind the seed
                     fwd_used[i] += 1
-                    appended[i] += len(committed)
-                    seq.clear_draft()
-                    if len(seq) != seq.num_cached_tokens:
-                        raise RuntimeError(f"Invariant violated: len(token_ids)={len(seq)} != num_cached_tokens={seq.num_cached_tokens}")
-                    first_new = blk.accept(committed)
-                    if stop_hit:                                                     # JDO:439-463
-                        kept = _truncate_after_stop(list(seq.token_ids), completion_start_lens[i], self.stop_token_ids)
-                        dropped = len(seq.token_ids) - len(kept)
-                        if dropped:
-                            seq.token_ids = kept
-                            if bm is not None:
-                                bm.trim_kv_only_fast(seq, dropped)
-                        blk.close_at_stop(first_new)
-                    elif blk.accepted < blk.gen_len:                                 # JDO:465-477 (samples drawn on the GPU)
-                        blk.refill(redraft[len(committed):])
-                    blk.snapshot()
+                    appended[i] += self._commit_row(seq, blocks[i], prop, row, committed, redraft, self.cursors_per_sequence[i],
+                                                    Lm, completion_start_lens[i])   # the forward cached Lm positions behind the seed
         return {i: (blocks[i].trajectory, appended[i], fwd_used[i], blocks[i].stopped) for i in rows}
 
     # ------------------------------------------------------------------------------- records (JDO:494-614)

@@ -1171,18 +1171,53 @@ class RsStepper:
 # --------------------------------------------------------------------------------------------
 # on-policy rollout step (JDO:270-327 verify + JDO:465-477 re-draft)
 # --------------------------------------------------------------------------------------------
-class OnPolicyStepper:
-    """jf_rs_probs + jf_rs_onpolicy_step for one sequence per call: three launches, one read-back."""
+class _OnPolicyCore:
+    """What the two on-policy steppers share: the per-row buffers of ``n`` rows, the stop ids, and the launches in front of the
+    step (jf_rs_probs reads the logits once; jf_rs_filter when top_k / top_p is active)."""
 
-    def __init__(self, max_L: int, device, u_stream, m_stream, stop_ids: Sequence[int]):
+    def __init__(self, n: int, device, stop_ids: Sequence[int]):
         dev = torch.device(device)
-        self.device, self.max_L = dev, int(max_L)
-        n = self.max_L
+        self.device = dev
         self.packed = new_packed(n, dev)
         f32 = lambda k: torch.zeros((k,), dtype=torch.float32, device=dev)
         self.p_draft, self.row_max, self.row_sumexp = f32(n), f32(n), f32(n)
         self.ws = torch.zeros((n * 16 * 2,), dtype=torch.float32, device=dev)     # grown to jf_rs_workspace_bytes(R, V) on demand
         self.step_ws = torch.zeros((int(N.lib().jf_rs_step_workspace_bytes(n)) // 8 + 2,), dtype=torch.float64, device=dev)
+        self.stop_ids = torch.tensor([int(x) for x in stop_ids], dtype=torch.int32, device=dev)
+        self.filter: Optional[RowFilter] = None
+
+    def _probs(self, logits: torch.Tensor, proposed: torch.Tensor, temperature: float, top_k: int, top_p: float):
+        """logits [n, V], proposed: n ids -> (the rows with unit inner stride, their row stride, the ids int64 on the device,
+        the filter records or None); p_draft / row_max / row_sumexp / packed are filled for the step."""
+        n, V = logits.shape
+        flat = logits if logits.stride(1) == 1 else logits.contiguous()
+        stride = flat.stride(0) if n > 1 else V
+        prop = proposed.to(device=self.device, dtype=torch.int64).contiguous()
+        lib = N.lib()
+        self.ws = _grown(self.ws, int(lib.jf_rs_workspace_bytes(n, V)))
+        N.check(lib.jf_rs_probs(_ptr(flat), _dtype_code(flat), n, V, stride, _ptr(prop), float(temperature), _ptr(self.p_draft),
+                                _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed), _ptr(self.ws), self.ws.numel() * 4,
+                                _stream(self.device)), "jf_rs_probs")
+        filt = None
+        if int(top_k) > 0 or float(top_p) > 0.0:
+            if self.filter is None:
+                self.filter = RowFilter(self.device)
+            filt = self.filter.run(flat, prop.view(-1), temperature, top_k, top_p, self.p_draft, self.row_max, self.row_sumexp)
+        return flat, stride, prop, filt
+
+    @staticmethod
+    def _record(ints) -> dict:
+        """one jf_op_row as a dict"""
+        return dict(zip(N.OP_FIELDS, (int(x) for x in ints)))
+
+
+class OnPolicyStepper(_OnPolicyCore):
+    """jf_rs_probs [+ jf_rs_filter] + jf_rs_onpolicy_step for one sequence per call: one read-back."""
+
+    def __init__(self, max_L: int, device, u_stream, m_stream, stop_ids: Sequence[int]):
+        self.max_L = n = int(max_L)
+        super().__init__(n, device, stop_ids)
+        dev = self.device
         self.out = torch.zeros((2, n), dtype=torch.int64, device=dev)              # committed, redraft
         self.row_dev = torch.zeros((N.OP_ROW_INTS,), dtype=torch.int32, device=dev)
         pin = dev.type == "cuda"
@@ -1190,7 +1225,6 @@ class OnPolicyStepper:
         self.out_host = torch.zeros((2, n), dtype=torch.int64, pin_memory=pin)
         self.u_stream = torch.as_tensor(u_stream).to(device=dev, dtype=torch.float32).contiguous()
         self.m_stream = torch.as_tensor(m_stream).to(device=dev, dtype=torch.float32).contiguous()
-        self.stop_ids = torch.tensor([int(x) for x in stop_ids], dtype=torch.int32, device=dev)
         self.cursors = torch.zeros((2,), dtype=torch.int64, device=dev)             # uniforms, multinomial
 
     def step(self, proposed: torch.Tensor, logits: torch.Tensor, temperature: float, cursors: Sequence[int], top_k: int = 0,
@@ -1204,23 +1238,13 @@ class OnPolicyStepper:
             raise RuntimeError("OnPolicyStepper capacity exceeded")
         dev = self.device
         V = logits.shape[-1]
-        flat = logits if logits.stride(1) == 1 else logits.contiguous()
-        prop = proposed.to(device=dev, dtype=torch.int64).contiguous()
-        lib = N.lib()
-        self.ws = _grown(self.ws, int(lib.jf_rs_workspace_bytes(R, V)))
-        N.check(lib.jf_rs_probs(_ptr(flat), _dtype_code(flat), R, V, flat.stride(0) if R > 1 else V, _ptr(prop),
-                                float(temperature), _ptr(self.p_draft), _ptr(self.row_max), _ptr(self.row_sumexp),
-                                _ptr(self.packed), _ptr(self.ws), self.ws.numel() * 4, _stream(dev)), "jf_rs_probs")
-        filt = None
-        if int(top_k) > 0 or float(top_p) > 0.0:
-            if getattr(self, "filter", None) is None:
-                self.filter = RowFilter(dev)
-            filt = self.filter.run(flat, prop, temperature, top_k, top_p, self.p_draft, self.row_max, self.row_sumexp)
+        flat, stride, prop, filt = self._probs(logits, proposed, temperature, top_k, top_p)
         self.cursors.copy_(torch.tensor(list(cursors), dtype=torch.int64), non_blocking=True)
         cur = self.cursors
         c_ptr = lambda i: C.c_void_p(cur.data_ptr() + 8 * i)
         cm, rd = self.out[0], self.out[1]
-        N.check(lib.jf_rs_onpolicy_step(_ptr(flat), _dtype_code(flat), V, flat.stride(0) if R > 1 else V, _ptr(prop), R,
+        lib = N.lib()
+        N.check(lib.jf_rs_onpolicy_step(_ptr(flat), _dtype_code(flat), V, stride, _ptr(prop), R,
                                         _ptr(self.p_draft), _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed),
                                         float(temperature), _ptr(self.stop_ids), int(self.stop_ids.numel()),
                                         _ptr(self.u_stream), self.u_stream.numel(), c_ptr(0),
@@ -1231,44 +1255,38 @@ class OnPolicyStepper:
         self.out_host[:, :R].copy_(self.out[:, :R], non_blocking=True)
         if dev.type == "cuda":
             torch.cuda.current_stream(dev).synchronize()
-        row = dict(zip(N.OP_FIELDS, self.row_host.tolist()))
+        row = self._record(self.row_host.tolist())
         n = row["n_committed"]
         return row, self.out_host[0, :n].tolist(), self.out_host[1, :R].tolist()
 
 
-class OnPolicyBatchStepper:
+class OnPolicyBatchStepper(_OnPolicyCore):
     """jf_rs_probs [+ jf_rs_filter] + jf_rs_onpolicy_step_batch for a group of sequences per call (lock-step rollouts): the
     number of launches does not depend on the group, one pinned read-back and one synchronise per forward.  Every sequence
     has its own two streams (concatenated once on the device) and its own two cursors, which stay on the device between
     forwards (``self.cursors`` [max_rows, 2]: uniforms, multinomial)."""
 
     def __init__(self, max_rows: int, max_L: int, device, u_streams, m_streams, stop_ids: Sequence[int]):
-        dev = torch.device(device)
-        self.device, self.max_rows, self.max_L = dev, int(max_rows), int(max_L)
+        self.max_rows, self.max_L = int(max_rows), int(max_L)
         if len(u_streams) != self.max_rows or len(m_streams) != self.max_rows:
             raise ValueError("OnPolicyBatchStepper needs one uniform and one multinomial stream per sequence")
-        n = self.max_rows * self.max_L
-        self.packed = new_packed(n, dev)
-        f32 = lambda k: torch.zeros((k,), dtype=torch.float32, device=dev)
-        self.p_draft, self.row_max, self.row_sumexp = f32(n), f32(n), f32(n)
-        self.ws = torch.zeros((n * 16 * 2,), dtype=torch.float32, device=dev)     # grown to jf_rs_workspace_bytes(R, V) on demand
-        self.step_ws = torch.zeros((int(N.lib().jf_rs_step_workspace_bytes(n)) // 8 + 2,), dtype=torch.float64, device=dev)
-        # one buffer for everything a forward reads back: committed [G, Lm] ⧺ redraft [G, Lm] ⧺ the G records (4 words each)
-        words = 2 * n + self.max_rows * (N.OP_ROW_INTS // 2)
-        self.out = torch.zeros((words,), dtype=torch.int64, device=dev)
-        self.out_host = torch.zeros((words,), dtype=torch.int64, pin_memory=dev.type == "cuda")
         us = [np.asarray(u, dtype=np.float32).reshape(-1) for u in u_streams]
         ms = [np.asarray(m, dtype=np.float32).reshape(-1) for m in m_streams]
         if any(a.size == 0 for a in us + ms):
             raise ValueError("OnPolicyBatchStepper: empty random stream")
+        n = self.max_rows * self.max_L
+        super().__init__(n, device, stop_ids)
+        dev = self.device
+        # one buffer for everything a forward reads back: committed [G, Lm] ⧺ redraft [G, Lm] ⧺ the G records (4 words each)
+        words = 2 * n + self.max_rows * (N.OP_ROW_INTS // 2)
+        self.out = torch.zeros((words,), dtype=torch.int64, device=dev)
+        self.out_host = torch.zeros((words,), dtype=torch.int64, pin_memory=dev.type == "cuda")
         self.u_stream = torch.from_numpy(np.concatenate(us)).to(dev)
         self.m_stream = torch.from_numpy(np.concatenate(ms)).to(dev)
         starts = lambda arrs: np.cumsum([0] + [a.size for a in arrs[:-1]])
         self.stream_off = torch.from_numpy(np.stack([starts(us), starts(ms)], 1).astype(np.int64)).to(dev)             # [max_rows, 2]
         self.stream_len = torch.from_numpy(np.array([[a.size, b.size] for a, b in zip(us, ms)], dtype=np.int64)).to(dev)
-        self.stop_ids = torch.tensor([int(x) for x in stop_ids], dtype=torch.int32, device=dev)
         self.cursors = torch.zeros((self.max_rows, 2), dtype=torch.int64, device=dev)
-        self.filter: Optional[RowFilter] = None
 
     def step(self, proposed: torch.Tensor, n_rows: Sequence[int], logits: torch.Tensor, temperature: float,
              seq_index: Sequence[int], top_k: int = 0, top_p: float = 0.0):
@@ -1285,22 +1303,8 @@ class OnPolicyBatchStepper:
         dev = self.device
         V = int(logits.shape[-1])
         n = G * Lm
-        flat = logits.reshape(n, V)
-        if flat.stride(1) != 1:
-            flat = flat.contiguous()
-        stride = flat.stride(0) if n > 1 else V
-        prop = proposed.to(device=dev, dtype=torch.int64).contiguous()
+        flat, stride, prop, filt = self._probs(logits.reshape(n, V), proposed, temperature, top_k, top_p)
         nr = torch.tensor([int(r) for r in n_rows], dtype=torch.int32).to(dev, non_blocking=True)
-        lib = N.lib()
-        self.ws = _grown(self.ws, int(lib.jf_rs_workspace_bytes(n, V)))
-        N.check(lib.jf_rs_probs(_ptr(flat), _dtype_code(flat), n, V, stride, _ptr(prop), float(temperature), _ptr(self.p_draft),
-                                _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed), _ptr(self.ws), self.ws.numel() * 4,
-                                _stream(dev)), "jf_rs_probs")
-        filt = None
-        if int(top_k) > 0 or float(top_p) > 0.0:
-            if self.filter is None:
-                self.filter = RowFilter(dev)
-            filt = self.filter.run(flat, prop.view(-1), temperature, top_k, top_p, self.p_draft, self.row_max, self.row_sumexp)
         whole = [int(i) for i in seq_index] == list(range(G))      # the first G sequences in order: their slices are the arrays
         if whole:
             off, ln, cur = self.stream_off[:G], self.stream_len[:G], self.cursors[:G]
@@ -1308,6 +1312,7 @@ class OnPolicyBatchStepper:
             idx = torch.tensor([int(i) for i in seq_index], dtype=torch.int64).to(dev, non_blocking=True)
             off, ln, cur = self.stream_off.index_select(0, idx), self.stream_len.index_select(0, idx), self.cursors.index_select(0, idx)
         cm, rd, rows = self.out[:n], self.out[n:2 * n], self.out[2 * n:2 * n + G * (N.OP_ROW_INTS // 2)]
+        lib = N.lib()
         N.check(lib.jf_rs_onpolicy_step_batch(_ptr(flat), _dtype_code(flat), V, stride, _ptr(prop), _ptr(nr), G, Lm,
                                               _ptr(self.p_draft), _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed),
                                               float(temperature), _ptr(self.stop_ids), int(self.stop_ids.numel()),
@@ -1324,7 +1329,7 @@ class OnPolicyBatchStepper:
         recs = host[2 * n:end].view(np.int32).reshape(G, N.OP_ROW_INTS)
         out_rows, out_cm, out_rd = [], [], []
         for g in range(G):
-            row = dict(zip(N.OP_FIELDS, (int(x) for x in recs[g])))
+            row = self._record(recs[g])
             if row["n_committed"] < 0:
                 raise RuntimeError(f"jf_rs_onpolicy_step_batch refused row {g} (row count or stream slice out of range)")
             out_rows.append(row)

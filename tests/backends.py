@@ -455,6 +455,42 @@ class HostSimLib:
         _view(packed, R, np.uint64)[:] = 0
         return 0
 
+    def jf_rs_onpolicy_step_batch(self, logits, dtype, V, stride, proposed, n_rows, G, Lm, p_draft, row_max, row_sumexp, packed,
+                                  temperature, stop_ids, n_stop, u_stream, m_stream, stream_off, stream_len, cursors, committed,
+                                  redraft, rows, ws, ws_bytes, filt, stream):
+        """A loop over the single-sequence stand-in: one call per sequence on that sequence's rows, cursors and stream window
+        (the definition of the batch entry point)."""
+        esz = 4 if dtype == N.JF_F32 else 2
+        nr = _view(n_rows, G, np.int32)
+        off = _view(stream_off, 2 * G, np.int64).reshape(G, 2)
+        ln = _view(stream_len, 2 * G, np.int64).reshape(G, 2)
+        fa = _addr(filt) if filt is not None else 0
+        dense = self._filtered.get(fa) if fa else None
+        at = lambda p, nbytes: _addr(p) + int(nbytes)
+        for g in range(G):
+            R, base = int(nr[g]), g * Lm
+            rec = at(rows, g * 4 * N.OP_ROW_INTS)
+            if not 1 <= R <= Lm or ln[g, 0] <= 0 or ln[g, 1] <= 0:
+                _view(rec, 1, np.int32)[0] = -1
+                continue
+            fg = None
+            if fa:
+                fg = fa + base * N.RS_FILTER_ROW_BYTES
+                self._filtered[fg] = dense[base:base + R]
+            rc = self.jf_rs_onpolicy_step(at(logits, base * stride * esz), dtype, V, stride, at(proposed, base * 8), R,
+                                          at(p_draft, base * 4), at(row_max, base * 4), at(row_sumexp, base * 4), at(packed, base * 8),
+                                          temperature, stop_ids, n_stop, at(u_stream, 4 * off[g, 0]), int(ln[g, 0]), at(cursors, 16 * g),
+                                          at(m_stream, 4 * off[g, 1]), int(ln[g, 1]), at(cursors, 16 * g + 8),
+                                          at(committed, base * 8), at(redraft, base * 8), rec, ws, ws_bytes, fg, stream)
+            if fg is not None and fg != fa:
+                del self._filtered[fg]
+            if rc:
+                return rc
+        if fa:
+            self._filtered[fa] = dense
+        _view(packed, G * Lm, np.uint64)[:] = 0
+        return 0
+
 
 @contextlib.contextmanager
 def use_backend(name: str):

@@ -2,7 +2,6 @@
 one forward (``jf_rs_onpolicy_step_batch``).  The contract: per sequence, the records, metrics, final token list, cached length
 and draw counts are what the sequential path gives for that sequence ALONE with its own streams — so every expected value here
 comes from the oracle (``O.onpolicy_rollout_records_batch``, pinned to the reference's goldens) called once per sequence."""
-import contextlib
 import inspect
 import re
 import subprocess
@@ -19,63 +18,12 @@ from jacobiforcing_amd.sampling_params import SamplingParams
 from oracle import jacobi_oracle as O
 from oracle.scripted_model import ScriptedModel
 
-from .backends import HostSimLib, _addr, _view, device_for
+from .backends import device_for, use_backend
 from .test_engine_decoder import JDO, TORCH_DTYPES, Harness
 
 ROOT = Path(__file__).resolve().parents[1]
 GPU = pytest.mark.gpu
 SYMBOL = "jf_rs_onpolicy_step_batch"
-
-
-# ------------------------------------------------------------------------------------- the stand-in
-class BatchSimLib(HostSimLib):
-    """HostSimLib + jf_rs_onpolicy_step_batch as a loop over the single-sequence stand-in: one call per sequence on that
-    sequence's rows, cursors and stream window (the definition of the batch entry point)."""
-
-    def jf_rs_onpolicy_step_batch(self, logits, dtype, V, stride, proposed, n_rows, G, Lm, p_draft, row_max, row_sumexp, packed,
-                                  temperature, stop_ids, n_stop, u_stream, m_stream, stream_off, stream_len, cursors, committed,
-                                  redraft, rows, ws, ws_bytes, filt, stream):
-        esz = 4 if dtype == N.JF_F32 else 2
-        nr = _view(n_rows, G, np.int32)
-        off = _view(stream_off, 2 * G, np.int64).reshape(G, 2)
-        ln = _view(stream_len, 2 * G, np.int64).reshape(G, 2)
-        fa = _addr(filt) if filt is not None else 0
-        dense = self._filtered.get(fa) if fa else None
-        at = lambda p, nbytes: _addr(p) + int(nbytes)
-        for g in range(G):
-            R, base = int(nr[g]), g * Lm
-            rec = at(rows, g * 4 * N.OP_ROW_INTS)
-            if not 1 <= R <= Lm or ln[g, 0] <= 0 or ln[g, 1] <= 0:
-                _view(rec, 1, np.int32)[0] = -1
-                continue
-            fg = None
-            if fa:
-                fg = fa + base * N.RS_FILTER_ROW_BYTES
-                self._filtered[fg] = dense[base:base + R]
-            rc = self.jf_rs_onpolicy_step(at(logits, base * stride * esz), dtype, V, stride, at(proposed, base * 8), R,
-                                          at(p_draft, base * 4), at(row_max, base * 4), at(row_sumexp, base * 4), at(packed, base * 8),
-                                          temperature, stop_ids, n_stop, at(u_stream, 4 * off[g, 0]), int(ln[g, 0]), at(cursors, 16 * g),
-                                          at(m_stream, 4 * off[g, 1]), int(ln[g, 1]), at(cursors, 16 * g + 8),
-                                          at(committed, base * 8), at(redraft, base * 8), rec, ws, ws_bytes, fg, stream)
-            if fg is not None and fg != fa:
-                del self._filtered[fg]
-            if rc:
-                return rc
-        if fa:
-            self._filtered[fa] = dense
-        _view(packed, G * Lm, np.uint64)[:] = 0
-        return 0
-
-
-@contextlib.contextmanager
-def use_lockstep_backend(name: str):
-    """tests.backends.use_backend with the stand-in that knows the batch entry point"""
-    old = N._LIB
-    N._LIB = BatchSimLib() if name == "hostsim" else N.load()
-    try:
-        yield N._LIB
-    finally:
-        N._LIB = old
 
 
 # ------------------------------------------------------------------------------------- 1. boundary
@@ -170,7 +118,7 @@ def _build(cfg, backend, **dec_kw):
 
 def _run_fuzz(seed, backend):
     cfg = _fuzz_setup(seed)
-    with use_lockstep_backend(backend):
+    with use_backend(backend):
         H, dec, seqs, models = _build(cfg, backend)
         inits = [O.CounterStream(9000 + it["seed"]) for it in cfg["items"]]
         dec.set_streams_per_sequence([O.ScriptedRandom(s) for s in inits], [it["unis"] for it in cfg["items"]],
@@ -237,7 +185,7 @@ def test_one_forward_carries_every_open_row(seed):
                   multi=[float(x) for x in (rng.integers(0, 1 << 24, size=2048) / float(1 << 24))]) for i in range(B)]
     items[2]["eos_pos"] = items[2]["pl"] + 6                       # one sequence stops early
     cfg = dict(V=V, eos=V - 1, pad=V - 2, stop_ids=[V - 1], ldt="f32", peak=8.0, robust=60, max_blocks=128, items=items)
-    with use_lockstep_backend("hostsim"):
+    with use_backend("hostsim"):
         H, dec, seqs, models = _build(cfg, "hostsim")
         dec.set_streams_per_sequence([O.ScriptedRandom(O.CounterStream(9000 + it["seed"])) for it in items],
                                      [it["unis"] for it in items], [it["multi"] for it in items])
@@ -293,7 +241,7 @@ def test_single_sequence_goldens_replay_in_lockstep(name):
     padded, so lock-step must give the reference's records, metrics, draw counts and forward inputs."""
     case = _BY_NAME[name]
     assert len(case["seqs"]) == 1
-    with use_lockstep_backend("hostsim"):
+    with use_backend("hostsim"):
         H, dec, seqs, (inits, unis, multi) = _golden_decoder(case, "hostsim")
         dr = case["draws"]
         dec.set_streams_per_sequence([O.ScriptedRandom(inits)], [[unis.uniform() for _ in range(dr["uniforms"] + 64)]],
@@ -315,7 +263,7 @@ def test_lockstep_is_opt_in():
     multi = [c for c in JDO if len(c["seqs"]) > 1][:2]
     assert len(multi) == 2
     for case in multi:
-        with use_lockstep_backend("hostsim"):
+        with use_backend("hostsim"):
             H, dec, seqs, (inits, unis, mult) = _golden_decoder(case, "hostsim")
             dr = case["draws"]
             dec.set_streams(O.ScriptedRandom(inits), [unis.uniform() for _ in range(dr["uniforms"] + 64)],
@@ -328,7 +276,7 @@ def test_lockstep_is_opt_in():
 # ------------------------------------------------------------------------------------- 8. errors
 def test_lockstep_errors():
     cfg = _fuzz_setup(3)
-    with use_lockstep_backend("hostsim"):
+    with use_backend("hostsim"):
         H, dec, seqs, _ = _build(cfg, "hostsim", forward_step_batch=None)
         with pytest.raises(ValueError, match="forward_step_batch"):
             dec.generate_rollout_records_batch(seqs, lockstep=True)
@@ -356,7 +304,7 @@ def test_a_row_that_padding_would_push_over_the_cache_bound_is_stepped_alone():
                                    multi=[float(x) for x in (rng.integers(0, 1 << 24, size=512) / float(1 << 24))])
     items = [mk(0, 40, 4, 4), mk(1, 10, 16, 16)]                   # sequence 0 ends at 44 positions; padded to 16 it would reach 56
     cfg = dict(V=64, eos=63, pad=62, stop_ids=[63], ldt="f32", peak=8.0, robust=60, max_blocks=1, items=items)
-    with use_lockstep_backend("hostsim"):
+    with use_backend("hostsim"):
         H, dec, seqs, models = _build(cfg, "hostsim")
         dec.max_forward_positions = 45
         dec.set_streams_per_sequence([O.ScriptedRandom(O.CounterStream(9000 + it["seed"])) for it in items],
@@ -397,9 +345,9 @@ def _planted_batch(dtype):
 
 
 def _step_planted(backend, b, temperature, top_k=0, top_p=0.0):
-    with use_lockstep_backend(backend):
+    with use_backend(backend):
         dev = device_for(backend)
-        st = ops.OnPolicyBatchStepper(b["G"], 16, dev, b["us"], b["ms"], [b["stop"]])
+        st = ops.OnPolicyBatchStepper(b["G"], max(16, b["Lm"]), dev, b["us"], b["ms"], [b["stop"]])
         st.cursors.copy_(torch.tensor(b["cur0"], dtype=torch.int64))
         rows, cm, rd = st.step(b["proposed"].to(dev), b["n_rows"], b["logits"].to(dev), temperature, list(range(b["G"])), top_k, top_p)
         return rows, cm, rd, st.cursors.cpu().tolist(), st.packed.cpu()
@@ -441,7 +389,7 @@ def test_a_row_count_outside_the_rectangle_is_refused_by_the_kernel():
     """n_rows is a device array the host cannot check: the accept launch marks such a sequence (n_committed = -1) and touches
     nothing else of it — its cursors stay, its neighbours are stepped."""
     b = _planted_batch(torch.float32)
-    with use_lockstep_backend("hip"):
+    with use_backend("hip"):
         dev = device_for("hip")
         st = ops.OnPolicyBatchStepper(b["G"], 16, dev, b["us"], b["ms"], [b["stop"]])
         st.cursors.copy_(torch.tensor(b["cur0"], dtype=torch.int64))
@@ -467,3 +415,108 @@ def test_a_row_count_outside_the_rectangle_is_refused_by_the_kernel():
         assert cur[1] == b["cur0"][1] and cur[3] == b["cur0"][3] and cur[0][0] == b["cur0"][0][0] + 12
         assert (cm[1] == -7).all() and (cm[3] == -7).all() and (rd[1] == -7).all() and (rd[3] == -7).all()
         assert int(st.packed[:G * Lm].abs().sum()) == 0
+
+
+# ------------------------------------------------------------------------------------- 12. the two entry points agree
+def _small_batch(n_rows, reject_at, stop_at, lens, cur0, seed):
+    """Ragged sequences at V = 64, float32, T = 1: every proposed id holds ~0.78 of its row and every uniform is below 0.5, so
+    a test accepts unless it is planted: ``reject_at`` {g: t} gives row t's proposed id ~1e-14, ``stop_at`` {g: t} proposes the
+    stop id there.  ``lens`` [(uniforms, multinomial)] and ``cur0`` per sequence; a stream shorter than its sequence wraps."""
+    G, Lm, V, stop = len(n_rows), max(n_rows), 64, 3
+    g = torch.Generator().manual_seed(seed)
+    proposed = torch.randint(4, V, (G, Lm), generator=g)
+    logits = torch.randn(G, Lm, V, generator=g) * 0.5
+    for q, t in stop_at.items():
+        proposed[q, t] = stop
+    for q in range(G):
+        proposed[q, n_rows[q]:] = 0                                  # padding (never read by the step)
+        logits[q, torch.arange(n_rows[q]), proposed[q, :n_rows[q]]] = float(np.log(4.0 * (V - 1)))
+    for q, t in reject_at.items():
+        logits[q, t, proposed[q, t]] = -30.0
+    us = [(torch.randint(0, 1 << 23, (lu,), generator=g).float() / float(1 << 24)).numpy() for lu, _ in lens]
+    ms = [(torch.randint(0, 1 << 24, (lm_,), generator=g).float() / float(1 << 24)).numpy() for _, lm_ in lens]
+    return dict(G=G, Lm=Lm, V=V, stop=stop, n_rows=list(n_rows), proposed=proposed, logits=logits, us=us, ms=ms, cur0=cur0)
+
+
+def _step_alone(backend, b, q, temperature, top_k=0, top_p=0.0):
+    """sequence q of the batch through the single-sequence entry point: its rows, its stream window, its starting cursors"""
+    with use_backend(backend):
+        dev = device_for(backend)
+        R = b["n_rows"][q]
+        st = ops.OnPolicyStepper(max(16, R), dev, b["us"][q], b["ms"][q], [b["stop"]])
+        row, cm, rd = st.step(b["proposed"][q, :R].to(dev), b["logits"][q, :R].to(dev), temperature, b["cur0"][q], top_k, top_p)
+        return row, cm, rd, st.cursors.cpu().tolist(), st.packed.cpu()
+
+
+def _assert_entries_agree(b, batch, alone):
+    rows, cm, rd, cur, pk = batch
+    assert int(pk[:b["G"] * b["Lm"]].abs().sum()) == 0
+    for q, (row1, cm1, rd1, cur1, pk1) in enumerate(alone):
+        R, n = b["n_rows"][q], rows[q]["n_committed"]
+        assert len(row1) == N.OP_ROW_INTS == 8 and row1 == rows[q], q
+        assert len(cm1) == n and cm1 == cm[q], q
+        assert len(rd1) == len(rd[q]) == R and rd1[n:] == rd[q][n:], q
+        assert cur1 == cur[q], q
+        assert int(pk1[:R].abs().sum()) == 0
+
+
+def _p_draft_on_the_gpu(b):
+    """jf_rs_probs once on the whole rectangle (float32, T = 1): the kernel's own float32 probability of every proposed id"""
+    with use_backend("hip"):
+        dev = torch.device(device_for("hip"))
+        n, V = b["G"] * b["Lm"], b["V"]
+        flat, prop = b["logits"].to(dev).reshape(n, V), b["proposed"].to(dev).contiguous()
+        lib, p = N.lib(), ops._ptr
+        p_draft, row_max, row_sumexp = (torch.zeros((n,), dtype=torch.float32, device=dev) for _ in range(3))
+        packed = ops.new_packed(n, dev)
+        ws = torch.zeros((int(lib.jf_rs_workspace_bytes(n, V)) // 4 + 4,), dtype=torch.float32, device=dev)
+        N.check(lib.jf_rs_probs(p(flat), N.JF_F32, n, V, V, p(prop), 1.0, p(p_draft), p(row_max), p(row_sumexp), p(packed), p(ws),
+                                ws.numel() * 4, ops._stream(dev)), "jf_rs_probs")
+        return p_draft.cpu().view(b["G"], b["Lm"])
+
+
+def _agree_chunk_boundaries():
+    """(a) row counts around the 64-lane ballot chunk and the 256-thread loop: 0 accepts its one row, 1 rejects at row 0, 2
+    commits a stop id at row 40, 3 rejects at row 64 (the first lane of the second chunk), 4 accepts all 257 from a uniform
+    stream of 100 (it wraps twice; so does sequence 1's multinomial stream of 40 under its 62 re-drafts)."""
+    b = _small_batch([1, 63, 64, 65, 257], {1: 0, 3: 64}, {2: 40}, [(32, 32), (96, 40), (128, 64), (80, 72), (100, 48)],
+                     [[7, 3], [90, 35], [11, 60], [79, 1], [33, 47]], 61)
+    return b, 1.0, 0, 0.0, dict(n_committed=[1, 1, 41, 65, 257], reject_pos=[-1, 0, -1, 64, -1], stop_hit=[0, 0, 1, 0, 0])
+
+
+def _agree_real_vocabulary():
+    """(b) the planted batch at V = 152064 in bfloat16 with a temperature and both filters"""
+    return _planted_batch(torch.bfloat16), 0.7, 50, 0.9, None
+
+
+def _agree_outside_lds():
+    """(c) more than RS_OP_STAGE = 2048 rows per sequence: the accept entries are recomputed per ballot and resolved tests go
+    through the patch table.  Sequence 0 rejects at row 2048 (one re-draft behind it); in sequence 1 the uniforms of three
+    tests EQUAL the kernel's float32 probability of their row — the tests a kernel may mark undecided and resolve exactly."""
+    b = _small_batch([2050, 2049], {0: 2048}, {}, [(4096, 4096), (4096, 4096)], [[5, 9], [17, 2]], 67)
+    pd = _p_draft_on_the_gpu(b)
+    for t in (5, 700, 2047):
+        b["us"][1][b["cur0"][1][0] + t] = float(pd[1, t])
+    return b, 1.0, 0, 0.0, dict(reject_pos_0=2048)
+
+
+@GPU
+@pytest.mark.parametrize("case", [_agree_chunk_boundaries, _agree_real_vocabulary, _agree_outside_lds],
+                         ids=["chunk_boundaries", "real_vocabulary", "outside_lds"])
+def test_the_single_and_the_batch_entry_point_agree(case):
+    """One jf_rs_onpolicy_step_batch call on a ragged batch against one jf_rs_onpolicy_step call per sequence (its rows, stream
+    window and starting cursors): the eight ints of every record, committed[:n], redraft[n:R], both cursors afterwards and
+    packed re-zeroed are identical; at V = 64 both are also what the host stand-in gives."""
+    b, temperature, top_k, top_p, planted = case()
+    batch = _step_planted("hip", b, temperature, top_k, top_p)
+    alone = [_step_alone("hip", b, q, temperature, top_k, top_p) for q in range(b["G"])]
+    _assert_entries_agree(b, batch, alone)
+    if planted is None:
+        return
+    sim = _step_planted("hostsim", b, temperature, top_k, top_p)
+    if "reject_pos_0" in planted:
+        assert sim[0][0]["reject_pos"] == planted["reject_pos_0"] and sim[0][0]["n_redraft"] == 1
+    else:
+        for k, want in planted.items():
+            assert [r[k] for r in sim[0]] == want, k
+    _assert_entries_agree(b, sim, alone)
