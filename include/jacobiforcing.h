@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* 600 also covers the two forward-glue entry points added after it (jf_attn_out_relayout, jf_forward_plan): additions only,
+ * every earlier signature is unchanged.  A client that needs them checks for the symbols (dlsym), not for a version. */
 #define JF_VERSION 600
 
 enum {
@@ -336,6 +338,29 @@ JF_API int jf_rope_kv_append(const void *qkv, int dtype, int64_t N, int32_t T, i
 /* SwiGLU gate of the MLP in one pass: out[m, i] = silu(gu[m, i]) * gu[m, I + i] for the fused gate/up projection output
  * gu [M, 2*I] (row-major), out [M, I].  fp32 arithmetic, one rounding; dtype JF_F32 or JF_BF16. */
 JF_API int jf_swiglu(const void *gu, int dtype, int64_t M, int64_t I, void *out, void *stream);
+
+/* Attention output back to token-major rows (forward glue, a copy: bits pass through unchanged).
+ *   in   [Rn, nkv, G*T, D], D contiguous, the three outer strides in ELEMENTS (each a multiple of 16 bytes' worth): what
+ *        attention returns for jf_rope_kv_append's q_out (query row = g*T + t).  A contiguous tensor has strides
+ *        nkv*G*T*D, G*T*D, D; torch's fused attention returns a view of [Rn, G*T, nkv, D]: G*T*nkv*D, D, nkv*D.
+ *   out  row r0*T of the [Ntok, nkv*G*D] activation the output projection reads:
+ *        out[(r*T + t), (kv*G + g)*D + d] = in[r, kv, g*T + t, d]
+ * D must be a whole number of 16-byte vectors (JF_E_INVALID otherwise), both pointers 16-byte aligned.  dtype JF_F32 or JF_BF16. */
+JF_API int jf_attn_out_relayout(const void *in, int dtype, int64_t Rn, int32_t T, int32_t nkv, int32_t G, int32_t D,
+                         int64_t in_r_stride, int64_t in_kv_stride, int64_t in_q_stride, void *out, void *stream);
+
+/* Everything the forward needs in front of its first GEMM besides the embedding, in one launch (contiguous cache layout).
+ * Inputs: positions [R*T], row_prompt / row_cand / row_len / kv_len_rows [R], all int32 (Qwen2Model.forward's arguments).
+ *   bias       [R, G*T, S_pad] in `dtype` (JF_F32 / JF_BF16), every element written: column s < S_cur of row g*T + t is 0 where
+ *              rel < 0 || (rel <= t && rel < row_len[r]) with rel = s - kv_len_rows[r], -inf elsewhere; columns S_cur..S_pad-1
+ *              are 0.  S_pad is a multiple of 16 bytes' worth of elements.
+ *   slot_main  [R*T]: row_prompt[r]*S_max + positions[r,t] where t < row_len[r] and row_cand[r] < 0, else -1
+ *   slot_cand  [R*T] or NULL (no candidate rows): row_cand[r]*T_max + t where t < row_len[r] and row r is a candidate row,
+ *              else -1.  n_main >= 0: rows n_main.. are the candidate rows (the loop's order); n_main < 0: row_cand[r] >= 0.
+ * The slots are what jf_rope_kv_append takes. */
+JF_API int jf_forward_plan(const int32_t *positions, const int32_t *row_prompt, const int32_t *row_cand, const int32_t *row_len,
+                    const int32_t *kv_len_rows, int32_t R, int32_t T, int32_t G, int32_t S_cur, int32_t S_pad, int64_t S_max,
+                    int64_t T_max, int32_t n_main, int dtype, void *bias, int64_t *slot_main, int64_t *slot_cand, void *stream);
 
 /* commit accepted candidate rows: for prompt p copy desc[p].kv_copy_len token rows from the
  * candidate scratch cand[(p*cand_rows + kv_src_row-1), :, 0:len] to main[p, :, kv_copy_dst: +len],

@@ -151,6 +151,8 @@ _SIGNATURES = {
     "jf_rope_kv_append": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                     _vp, _i64, _vp]),
     "jf_swiglu": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
+    "jf_attn_out_relayout": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "jf_forward_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, C.c_int, _vp, _vp, _vp, _vp]),
     "jf_kv_commit": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, C.c_int, _i32, _i32, _i32, _i64, _i64, _i32, _vp]),
     "jf_engine_step": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "jf_sb_step": (C.c_int, [_vp, C.c_int, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),

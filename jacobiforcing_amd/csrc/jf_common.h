@@ -6,7 +6,7 @@
 //   jf_argmax_dev.h   device bodies of the argmax items, shared with the fused verify launch
 //   jf_multiblock.hip (a1, a4-a12) the multiblock Jacobi state machine kernels (jf_mb_*), one wavefront per prompt, and
 //                     jf_mb_verify: argmax items + per-prompt state-machine steps in ONE launch
-//   jf_kv.hip         (a18) KV append, fused RoPE + append, SwiGLU; (a9/a10) KV commit
+//   jf_kv.hip         (a18) KV append, fused RoPE + append, SwiGLU, attention-output re-layout, forward plan; (a9/a10) KV commit
 //   jf_engine.hip     (a15) engine single-block step, (a16) paged-KV index fill
 //   jf_sampling.hip   (a19) non-greedy verify (jf_rs_probs, jf_rs_step) and the on-policy rollout step
 #ifndef JF_COMMON_H

@@ -1,5 +1,5 @@
-// jf_kv.hip — (a18) KV append, fused RoPE + query re-layout + KV append, SwiGLU gate; (a9/a10) KV commit of the winning
-// candidate row.
+// jf_kv.hip — (a18) KV append, fused RoPE + query re-layout + KV append, SwiGLU gate, attention-output re-layout, forward
+// plan (mask + slots); (a9/a10) KV commit of the winning candidate row.
 #include "jf_common.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -275,6 +275,118 @@ extern "C" int jf_swiglu(const void *gu, int dtype, int64_t M, int64_t I, void *
     if (dtype == JF_F32) swiglu_kernel<float, 4><<<grid, block, 0, (hipStream_t)stream>>>((const float *)gu, M, I, (float *)out);
     else swiglu_kernel<uint16_t, 8><<<grid, block, 0, (hipStream_t)stream>>>((const uint16_t *)gu, M, I, (uint16_t *)out);
     return check_launch("swiglu_kernel");
+}
+
+// ---- attention-output re-layout: SDPA's [Rn, nkv, G*T, D] (query row g*T + t per KV head) back to the token-major
+// [Rn*T, nkv*G*D] activation the output projection reads.  Pure data movement: one 16-byte load and one 16-byte store per
+// lane.  Lanes are numbered along the OUTPUT, which is contiguous over a sequence, so a wavefront stores 1 KiB in one piece
+// (whole D-runs of one output row) and loads it as D-runs of (g, t) rows (256 B each for bf16 / D = 128).  The input's three
+// outer strides are arguments: torch's fused attention returns the [Rn, nkv, G*T, D] tensor as a view of [Rn, G*T, nkv, D].
+template <typename T, int EPV>
+__global__ __launch_bounds__(256) void attn_out_relayout_kernel(const T *__restrict__ in, int Tlen, int nkv, int G, int D,
+                                                                 int64_t s_r, int64_t s_kv, int64_t s_q, unsigned chunks,
+                                                                 T *__restrict__ out) {
+    const unsigned lph = (unsigned)(D / EPV);                 // lanes per head
+    const unsigned nq = (unsigned)(nkv * G);
+    const unsigned per_seq = (unsigned)Tlen * nq * lph;        // vectors of one sequence's [T, nq, D] output
+    const unsigned r = blockIdx.x / chunks;
+    const unsigned v = (blockIdx.x - r * chunks) * 256u + threadIdx.x;
+    if (v >= per_seq) return;
+    const unsigned th = v / lph, l = v - th * lph;
+    const unsigned t = th / nq, h = th - t * nq;
+    const unsigned kv = h / (unsigned)G, g = h - kv * (unsigned)G;
+    const T *src = in + r * s_r + kv * s_kv + (int64_t)(g * (unsigned)Tlen + t) * s_q + l * EPV;
+    T *dst = out + ((int64_t)r * per_seq + v) * EPV;
+    *reinterpret_cast<u32x4 *>(dst) = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src));
+}
+
+extern "C" int jf_attn_out_relayout(const void *in, int dtype, int64_t Rn, int32_t T, int32_t nkv, int32_t G, int32_t D,
+                                    int64_t in_r_stride, int64_t in_kv_stride, int64_t in_q_stride, void *out, void *stream) {
+    if (Rn <= 0 || T <= 0) return JF_OK;
+    if (!in || !out) return fail(JF_E_INVALID, "jf_attn_out_relayout: null pointer");
+    const int epv = dtype == JF_F32 ? 4 : 8;
+    if ((dtype != JF_F32 && dtype != JF_BF16) || nkv <= 0 || G <= 0 || D <= 0 || D % epv != 0 || ((uintptr_t)in) % 16 || ((uintptr_t)out) % 16 ||
+        in_r_stride < 0 || in_kv_stride < D || in_q_stride < D || in_r_stride % epv || in_kv_stride % epv || in_q_stride % epv)
+        return fail(JF_E_INVALID, "jf_attn_out_relayout: dtype/shape/alignment (D and the strides must be multiples of %d)", epv);
+    const int64_t per_seq = (int64_t)T * nkv * G * (D / epv);
+    const int64_t chunks = (per_seq + 255) / 256;             // workgroups per sequence
+    if (per_seq > 0x7FFFFFFFll || Rn * chunks > 0x7FFFFFFFll) return fail(JF_E_CAPACITY, "jf_attn_out_relayout: grid too large");
+    const dim3 grid((unsigned)(Rn * chunks)), block(256);
+    if (dtype == JF_F32)
+        attn_out_relayout_kernel<float, 4><<<grid, block, 0, (hipStream_t)stream>>>((const float *)in, T, nkv, G, D, in_r_stride, in_kv_stride,
+                                                                            in_q_stride, (unsigned)chunks, (float *)out);
+    else
+        attn_out_relayout_kernel<uint16_t, 8><<<grid, block, 0, (hipStream_t)stream>>>((const uint16_t *)in, T, nkv, G, D, in_r_stride, in_kv_stride,
+                                                                                      in_q_stride, (unsigned)chunks, (uint16_t *)out);
+    return check_launch("attn_out_relayout_kernel");
+}
+
+// ---- forward plan: what the forward needs in front of its first GEMM besides the embedding, in one launch: the additive
+// attention mask of every row (already repeated over the G query heads of a KV head, in the model dtype, S_pad-strided) and
+// the cache slots of the new K/V rows.  Integer compares and stores only.  A lane forms EPV mask values of one (r, t, s..)
+// and stores the vector G times: for a fixed g the (t, s) plane of a row is contiguous, so lane v writes vector v of it.
+template <typename T, int EPV>
+__global__ __launch_bounds__(256) void forward_plan_kernel(const int32_t *__restrict__ positions, const int32_t *__restrict__ row_prompt,
+                                                            const int32_t *__restrict__ row_cand, const int32_t *__restrict__ row_len,
+                                                            const int32_t *__restrict__ kv_len_rows, int Tlen, int G, int S_cur, int S_pad,
+                                                            unsigned chunks, int64_t S_max, int64_t T_max, int n_main,
+                                                            T *__restrict__ bias, int64_t *__restrict__ slot_main,
+                                                            int64_t *__restrict__ slot_cand) {
+    constexpr T NEG_INF = sizeof(T) == 2 ? (T)0xFF80u : (T)0xFF800000u;
+    const unsigned r = blockIdx.x / chunks, c = blockIdx.x - r * chunks;
+    const int rlen = row_len[r], kvl = kv_len_rows[r];
+    if (c == 0) {                                              // the row's slots: its first workgroup
+        const int rc = row_cand[r];
+        const int64_t rp = row_prompt[r];
+        const bool cand = n_main >= 0 ? (int)r >= n_main : rc >= 0;
+        for (int t = threadIdx.x; t < Tlen; t += 256) {
+            const int64_t i = (int64_t)r * Tlen + t;
+            const bool valid = t < rlen;
+            slot_main[i] = (valid && rc < 0) ? rp * S_max + positions[i] : -1;
+            if (slot_cand) slot_cand[i] = (valid && cand) ? (int64_t)rc * T_max + t : -1;
+        }
+    }
+    const unsigned vps = (unsigned)(S_pad / EPV);              // vectors per mask row
+    const unsigned plane = (unsigned)Tlen * vps;               // vectors of one (r, g) plane [T, S_pad]
+    const unsigned v = c * 256u + threadIdx.x;
+    if (v >= plane) return;
+    const int t = (int)(v / vps), s0 = (int)(v - (unsigned)t * vps) * EPV;
+    alignas(16) T w[EPV];
+#pragma unroll
+    for (int j = 0; j < EPV; ++j) {
+        const int s = s0 + j, rel = s - kvl;                   // key index relative to the new block
+        const bool keep = s >= S_cur || rel < 0 || (rel <= t && rel < rlen);
+        w[j] = keep ? (T)0 : NEG_INF;
+    }
+    T *dst = bias + ((int64_t)r * G * plane + v) * EPV;
+    for (int g = 0; g < G; ++g) *reinterpret_cast<uint4 *>(dst + (int64_t)g * plane * EPV) = *reinterpret_cast<const uint4 *>(w);
+}
+
+extern "C" int jf_forward_plan(const int32_t *positions, const int32_t *row_prompt, const int32_t *row_cand, const int32_t *row_len,
+                               const int32_t *kv_len_rows, int32_t R, int32_t T, int32_t G, int32_t S_cur, int32_t S_pad, int64_t S_max,
+                               int64_t T_max, int32_t n_main, int dtype, void *bias, int64_t *slot_main, int64_t *slot_cand,
+                               void *stream) {
+    if (R <= 0 || T <= 0) return JF_OK;
+    if (!positions || !row_prompt || !row_cand || !row_len || !kv_len_rows || !bias || !slot_main)
+        return fail(JF_E_INVALID, "jf_forward_plan: null pointer");
+    const int epv = dtype == JF_F32 ? 4 : 8;
+    if ((dtype != JF_F32 && dtype != JF_BF16) || G <= 0 || S_cur <= 0 || S_pad < S_cur || S_pad % epv != 0 || ((uintptr_t)bias) % 16 ||
+        S_max <= 0 || (slot_cand && T_max <= 0))
+        return fail(JF_E_INVALID, "jf_forward_plan: dtype/shape/alignment (R=%d T=%d G=%d S_cur=%d S_pad=%d, S_pad a multiple of %d)", R, T, G,
+                    S_cur, S_pad, epv);
+    const int64_t plane = (int64_t)T * (S_pad / epv);
+    const int64_t chunks = (plane + 255) / 256;               // workgroups per row
+    if (plane > 0x7FFFFFFFll || R * chunks > 0x7FFFFFFFll) return fail(JF_E_CAPACITY, "jf_forward_plan: grid too large");
+    const dim3 grid((unsigned)(R * chunks)), block(256);
+    if (dtype == JF_F32)
+        forward_plan_kernel<uint32_t, 4><<<grid, block, 0, (hipStream_t)stream>>>(positions, row_prompt, row_cand, row_len, kv_len_rows, T, G, S_cur,
+                                                                                 S_pad, (unsigned)chunks, S_max, T_max, n_main, (uint32_t *)bias,
+                                                                                 slot_main, slot_cand);
+    else
+        forward_plan_kernel<uint16_t, 8><<<grid, block, 0, (hipStream_t)stream>>>(positions, row_prompt, row_cand, row_len, kv_len_rows, T, G, S_cur,
+                                                                                 S_pad, (unsigned)chunks, S_max, T_max, n_main, (uint16_t *)bias,
+                                                                                 slot_main, slot_cand);
+    return check_launch("forward_plan_kernel");
 }
 
 __global__ __launch_bounds__(256) void kv_commit_kernel(void *const *main_k, void *const *main_v, void *const *cand_k,

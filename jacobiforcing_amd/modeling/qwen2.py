@@ -27,6 +27,10 @@ import torch.nn.functional as F
 
 from .. import ops
 
+# A/B switch (read once): 0 keeps the torch prelude and the torch attention-output copy on the GPU too.  Off the GPU the torch
+# code is the only path.
+FORWARD_GLUE = os.environ.get("JF_FORWARD_GLUE", "1") != "0"
+
 
 @dataclass
 class Qwen2Config:
@@ -277,7 +281,8 @@ class Qwen2Model:
                 paged_slots: Optional[torch.Tensor] = None, block_tables: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One forward over R rows of (padded) length T.
 
-        input_ids [R,T] int64, positions [R,T] int32 (= kv_len + t), row_prompt [R] (cache row of the prefix),
+        input_ids [R,T] int64, positions [R,T] int32 (= kv_len + t), the four per-row arrays int32 like positions (other integer
+        types work, at the price of a conversion launch each on the GPU): row_prompt [R] (cache row of the prefix),
         row_cand [R] (-1: the row writes into the main cache, else index into the candidate scratch),
         row_len [R] valid tokens per row, kv_len_rows [R] committed prefix length per row, s_cur = max(kv_len)+T when the
         caller knows it (saves a device read), rows_in_place = False when row r is NOT cache row r although R == P (a
@@ -297,7 +302,6 @@ class Qwen2Model:
         nq, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         G = nq // nkv
         dev = self.device
-        pos = positions.long()
         if s_cur is None:
             s_cur = (int(kv_len_rows.max().item()) + T) if R else T
         paged = block_tables is not None
@@ -305,55 +309,76 @@ class Qwen2Model:
         S_cur = min(int(s_cur), S_cap)
         if self.cos.shape[0] < S_cap:                        # a cache longer than max_position_embeddings: never read past the table
             self._rope_tables(S_cap)
-        ar_t = torch.arange(T, device=dev)
-        ar_s = torch.arange(S_cur, device=dev)
-        kvl = kv_len_rows.long()
-        rlen = row_len.long()
-        rel = ar_s.view(1, 1, S_cur) - kvl.view(R, 1, 1)                            # key index relative to the new block
-        mask = (rel < 0) | ((rel <= ar_t.view(1, T, 1)) & (rel < rlen.view(R, 1, 1)))
-        mask = mask.view(R, 1, 1, T, S_cur).expand(R, 1, G, T, S_cur).reshape(R, 1, G * T, S_cur)
-        # additive mask built once per forward (a bool mask is converted inside every SDPA call otherwise), as a view of a
-        # buffer whose row stride is a multiple of 16 elements: SDPA otherwise pads it itself — a fill and a copy in front of
-        # EVERY layer's attention kernel (tools/sdpa_probe.py: 6.6 + 7.8 us per layer at 64 prompts)
-        S_pad = (S_cur + 15) // 16 * 16
-        bias = torch.zeros((R, 1, G * T, S_pad), dtype=self.dtype, device=dev)[..., :S_cur]
-        bias.masked_fill_(~mask, float("-inf"))
-        # slots of the freshly computed K/V rows
-        valid = ar_t.view(1, T) < rlen.view(R, 1)
-        main_rows = row_cand < 0
-        neg = torch.full_like(pos, -1)
-        if paged:
-            if any_candidates or n_main is not None:
-                raise NotImplementedError("candidate rows over the paged layout (the engine's decoders are single-block: MR:1468-1473)")
-            slot_main = paged_slots.long().reshape(-1)
-            nblk = -(-S_cur // cache.S_max)
-            bt = block_tables[:, :nblk].clamp(min=0).long()                           # (blocks a row does not have: masked keys)
-        else:
-            slot_main = torch.where(valid & main_rows.view(R, 1), row_prompt.long().view(R, 1) * cache.S_max + pos, neg).reshape(-1)
-        rp = row_prompt.long()
+        pos32 = positions.to(torch.int32).reshape(-1).contiguous()
         split = n_main is not None
+        if paged and (any_candidates or split):
+            raise NotImplementedError("candidate rows over the paged layout (the engine's decoders are single-block: MR:1468-1473)")
         if split:
             RA = int(n_main)
             RB = R - RA
             any_candidates = RB > 0
             direct_a = RA == cache.P and rows_in_place is not False
-            if RB:
+        direct = (not paged) and (not any_candidates) and R == cache.P and rows_in_place is not False   # row r is cache row r: attend in place
+        # forward glue in HIP (GPU, contiguous layout): the mask and the slots come out of one launch (jf_forward_plan) and the
+        # attention output goes back to token-major rows in one 16-byte-per-lane copy (jf_attn_out_relayout).  The torch code
+        # in the else branch stays what the CPU path and the paged layout run, and is what both kernels are tested against, bit
+        # for bit.  Only the mask and the slots differ between the branches; the gather indices below them are shared.
+        glue = FORWARD_GLUE and dev.type == "cuda" and not paged and R > 0
+        if glue:
+            i32 = lambda t: t.to(torch.int32).contiguous()              # no launch for the int32 arrays every caller passes
+            bias, slot_main, slot_cand = ops.forward_plan(pos32, i32(row_prompt), i32(row_cand), i32(row_len), i32(kv_len_rows), T, G,
+                                                          S_cur, cache.S_max, cache.T_max, self.dtype, bool(any_candidates), n_main)
+            bias = bias[..., :S_cur]
+        else:
+            pos = positions.long()
+            ar_t = torch.arange(T, device=dev)
+            ar_s = torch.arange(S_cur, device=dev)
+            kvl = kv_len_rows.long()
+            rlen = row_len.long()
+            rel = ar_s.view(1, 1, S_cur) - kvl.view(R, 1, 1)                            # key index relative to the new block
+            mask = (rel < 0) | ((rel <= ar_t.view(1, T, 1)) & (rel < rlen.view(R, 1, 1)))
+            mask = mask.view(R, 1, 1, T, S_cur).expand(R, 1, G, T, S_cur).reshape(R, 1, G * T, S_cur)
+            # additive mask built once per forward (a bool mask is converted inside every SDPA call otherwise), as a view of a
+            # buffer whose row stride is a multiple of 16 elements: SDPA otherwise pads it itself — a fill and a copy in front of
+            # EVERY layer's attention kernel (tools/sdpa_probe.py: 6.6 + 7.8 us per layer at 64 prompts)
+            S_pad = (S_cur + 15) // 16 * 16
+            bias = torch.zeros((R, 1, G * T, S_pad), dtype=self.dtype, device=dev)[..., :S_cur]
+            bias.masked_fill_(~mask, float("-inf"))
+            # slots of the freshly computed K/V rows
+            valid = ar_t.view(1, T) < rlen.view(R, 1)
+            main_rows = row_cand < 0
+            neg = torch.full_like(pos, -1)
+            if paged:
+                slot_main = paged_slots.long().reshape(-1)
+            else:
+                slot_main = torch.where(valid & main_rows.view(R, 1), row_prompt.long().view(R, 1) * cache.S_max + pos, neg).reshape(-1)
+            if split and RB:
                 slot_cand = torch.where(valid[RA:], row_cand[RA:].long().view(RB, 1) * cache.T_max + ar_t.view(1, T), neg[RA:])
                 slot_cand = torch.cat([neg[:RA].reshape(-1), slot_cand.reshape(-1)])
-                tail_idx = (kvl[RA:].view(-1, 1) + ar_t.view(1, T)).clamp_(max=S_cur - 1).view(-1, 1, T, 1).expand(-1, nkv, T, hd)
-                crc, rp_b = row_cand[RA:].long(), rp[RA:]
+            elif any_candidates:
+                slot_cand = torch.where(valid & (~main_rows).view(R, 1), row_cand.long().view(R, 1) * cache.T_max + ar_t.view(1, T),
+                                        neg).reshape(-1)
+        # which K/V rows each row attends over: gather indices, formed only where a row is not its cache row in place
+        def tail_index(kv_rows):          # [C] committed lengths -> where the C candidate rows' own T new keys sit among the S_cur keys
+            idx = (kv_rows.long().view(-1, 1) + torch.arange(T, device=dev).view(1, T)).clamp_(max=S_cur - 1)
+            return idx.view(-1, 1, T, 1).expand(-1, nkv, T, hd)
+        if paged:
+            nblk = -(-S_cur // cache.S_max)
+            bt = block_tables[:, :nblk].clamp(min=0).long()                               # (blocks a row does not have: masked keys)
+        elif split:
+            if RB:
+                tail_idx = tail_index(kv_len_rows[RA:])
+                crc, rp_b = row_cand[RA:].long(), row_prompt[RA:].long()
             if not direct_a:
-                rp_a = rp[:RA]
+                rp_a = row_prompt[:RA].long()
         elif any_candidates:
-            slot_cand = torch.where(valid & (~main_rows).view(R, 1), row_cand.long().view(R, 1) * cache.T_max + ar_t.view(1, T),
-                                    neg).reshape(-1)
-            cr = (~main_rows).nonzero(as_tuple=True)[0]
+            rp = row_prompt.long()
+            cr = (row_cand >= 0).nonzero(as_tuple=True)[0]
             if cr.numel():
-                tail_idx = (kvl[cr].view(-1, 1) + ar_t.view(1, T)).clamp_(max=S_cur - 1)          # [C,T]
-                tail_idx = tail_idx.view(-1, 1, T, 1).expand(-1, nkv, T, hd)
+                tail_idx = tail_index(kv_len_rows[cr])
                 crc = row_cand[cr].long()
-        pos32 = positions.to(torch.int32).reshape(-1).contiguous()
-        direct = (not paged) and (not any_candidates) and R == cache.P and rows_in_place is not False   # row r is cache row r: attend in place
+        elif not direct:
+            rp = row_prompt.long()
 
         x = w.embed[input_ids].view(R * T, cfg.hidden_size)                           # [R*T, H]
         for li, L in enumerate(w.layers):
@@ -369,13 +394,19 @@ class Qwen2Model:
                     Ka, Va = cache.k[li][rp_a, :, :S_cur], cache.v[li][rp_a, :, :S_cur]
                 oa = F.scaled_dot_product_attention(qh[:RA], Ka, Va, attn_mask=bias[:RA])
                 o = torch.empty((R * T, nq * hd), dtype=oa.dtype, device=dev)
-                o[:RA * T].view(RA, T, nkv, G, hd).copy_(oa.view(RA, nkv, G, T, hd).permute(0, 3, 1, 2, 4))
+                if glue:
+                    ops.attn_out_relayout(oa, T, G, o[:RA * T])
+                else:
+                    o[:RA * T].view(RA, T, nkv, G, hd).copy_(oa.view(RA, nkv, G, T, hd).permute(0, 3, 1, 2, 4))
                 if RB:
                     # candidate rows: the prompt's prefix (gathered for these rows only) with their own speculative tail
                     Kb = cache.k[li][rp_b, :, :S_cur].scatter_(2, tail_idx, cache.ck[li][crc, :, :T])
                     Vb = cache.v[li][rp_b, :, :S_cur].scatter_(2, tail_idx, cache.cv[li][crc, :, :T])
                     ob = F.scaled_dot_product_attention(qh[RA:], Kb, Vb, attn_mask=bias[RA:])
-                    o[RA * T:].view(RB, T, nkv, G, hd).copy_(ob.view(RB, nkv, G, T, hd).permute(0, 3, 1, 2, 4))
+                    if glue:
+                        ops.attn_out_relayout(ob, T, G, o[RA * T:])
+                    else:
+                        o[RA * T:].view(RB, T, nkv, G, hd).copy_(ob.view(RB, nkv, G, T, hd).permute(0, 3, 1, 2, 4))
                 x.addmm_(o, L["wo"].t())
                 x = self._mlp_residual(L, x, self._norm(x, L["ln2"]))
                 continue
@@ -394,7 +425,10 @@ class Qwen2Model:
             else:
                 Kf, Vf = cache.k[li][rp, :, :S_cur], cache.v[li][rp, :, :S_cur]
             o = F.scaled_dot_product_attention(qh, Kf, Vf, attn_mask=bias)
-            o = o.view(R, nkv, G, T, hd).permute(0, 3, 1, 2, 4).reshape(R * T, nq * hd)
+            if glue:
+                o = ops.attn_out_relayout(o, T, G, torch.empty((R * T, nq * hd), dtype=o.dtype, device=dev))
+            else:
+                o = o.view(R, nkv, G, T, hd).permute(0, 3, 1, 2, 4).reshape(R * T, nq * hd)
             x.addmm_(o, L["wo"].t())                                                  # residual in the GEMM epilogue, in place
             x = self._mlp_residual(L, x, self._norm(x, L["ln2"]))
         flat = self._norm(x, w.norm)

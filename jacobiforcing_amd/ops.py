@@ -623,6 +623,43 @@ def swiglu(gu: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def attn_out_relayout(oa: torch.Tensor, T: int, G: int, out_rows: torch.Tensor) -> torch.Tensor:
+    """Attention output [Rn, nkv, G*T, D] -> its rows ``out_rows`` [Rn*T, nkv*G*D] of the token-major activation (one HIP
+    launch; what ``out_rows.view(Rn, T, nkv, G, D).copy_(oa.view(Rn, nkv, G, T, D).permute(0, 3, 1, 2, 4))`` does).  ``oa`` is
+    read through its strides (the fused attention returns a transposed view), only D has to be contiguous."""
+    if oa.dim() != 4 or oa.shape[2] != G * T or (oa.shape[3] > 1 and oa.stride(3) != 1):
+        raise ValueError("attn_out_relayout expects a [Rn, nkv, G*T, D] tensor with contiguous D")
+    Rn, nkv, _, D = oa.shape
+    s_r, s_kv, s_q = (oa.stride(i) if oa.shape[i] > 1 else D for i in range(3))     # a size-1 dimension's stride is never used
+    if (out_rows.dim() != 2 or not out_rows.is_contiguous() or tuple(out_rows.shape) != (Rn * T, nkv * G * D)
+            or out_rows.dtype != oa.dtype or out_rows.device != oa.device):
+        raise ValueError("attn_out_relayout: out_rows must be contiguous [Rn*T, nkv*G*D] rows of oa's dtype and device")
+    N.check(N.lib().jf_attn_out_relayout(_ptr(oa), _dtype_code(oa), Rn, T, nkv, G, D, s_r, s_kv, s_q, _ptr(out_rows), _stream(oa.device)),
+            "jf_attn_out_relayout")
+    return out_rows
+
+
+def forward_plan(positions: torch.Tensor, row_prompt: torch.Tensor, row_cand: torch.Tensor, row_len: torch.Tensor,
+                 kv_len_rows: torch.Tensor, T: int, G: int, S_cur: int, S_max: int, T_max: int, dtype: torch.dtype,
+                 with_cand: bool, n_main: Optional[int] = None):
+    """The forward's prelude in one HIP launch (jf_forward_plan): the additive attention mask as its S_pad-strided buffer
+    [R, 1, G*T, S_pad] (the caller attends over ``[..., :S_cur]``), slot_main [R*T] int64 and, ``with_cand``, slot_cand [R*T].
+    positions [R*T] and the four per-row arrays [R] are contiguous int32."""
+    R = row_len.numel()
+    dev = positions.device
+    for t, n in ((positions, R * T), (row_prompt, R), (row_cand, R), (row_len, R), (kv_len_rows, R)):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != dev:
+            raise ValueError("forward_plan: positions [R*T] and the per-row arrays [R] must be contiguous int32 on one device")
+    S_pad = (S_cur + 15) // 16 * 16
+    bias = torch.empty((R, 1, G * T, S_pad), dtype=dtype, device=dev)
+    slot_main = torch.empty((R * T,), dtype=torch.int64, device=dev)
+    slot_cand = torch.empty((R * T,), dtype=torch.int64, device=dev) if with_cand else None
+    N.check(N.lib().jf_forward_plan(_ptr(positions), _ptr(row_prompt), _ptr(row_cand), _ptr(row_len), _ptr(kv_len_rows), R, T, G,
+                                    S_cur, S_pad, S_max, T_max, -1 if n_main is None else int(n_main), _dtype_code(bias), _ptr(bias),
+                                    _ptr(slot_main), _ptr(slot_cand), _stream(dev)), "jf_forward_plan")
+    return bias, slot_main, slot_cand
+
+
 class KVCommitter:
     """Holds the per-layer pointer tables for jf_kv_commit (candidate row -> committed row, MB:500-502)."""
 
