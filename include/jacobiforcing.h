@@ -31,8 +31,9 @@
 extern "C" {
 #endif
 
-/* 600 also covers the two forward-glue entry points added after it (jf_attn_out_relayout, jf_forward_plan): additions only,
- * every earlier signature is unchanged.  A client that needs them checks for the symbols (dlsym), not for a version. */
+/* 600 also covers the entry points added after it (the forward glue: jf_attn_out_relayout, jf_forward_plan; the autoregressive
+ * sampler: jf_rs_draw_workspace_bytes, jf_rs_draw_rows): additions only, every earlier signature is unchanged.  A client that
+ * needs them checks for the symbols (dlsym), not for a version. */
 #define JF_VERSION 600
 
 enum {
@@ -649,6 +650,26 @@ JF_API int jf_rs_onpolicy_step_batch(const void *logits, int dtype, int64_t V, i
                         int64_t *committed /* [G, Lm] */, int64_t *redraft /* [G, Lm] */, jf_op_row *rows /* [G] */,
                         void *workspace /* jf_rs_step_workspace_bytes(G * Lm) */, size_t workspace_bytes,
                         const jf_rs_filter_row *filt /* nullable: jf_rs_filter's records of the G * Lm rows */, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * One token per row from one uniform per row: the sampler of autoregressive requests (ops.ARSampler).  logits [R, V];
+ * row_max / row_sumexp [R] from jf_rs_probs on the same rows (draft_next may be zeros), or as jf_rs_filter has marked them
+ * when filt (its records of the R rows) is given.  For row r:
+ *   tokens[r] = the smallest id whose float64 running sum of p[r], in vocabulary order, exceeds u[r] * total
+ * where p[r] is the row's distribution as defined above (exactly rounded to the dtype, then filtered when filt is given) and
+ * total its float64 sum: the inverse CDF of the bonus and re-draft draws, with nothing avoided and no stream cursor.  In oracle
+ * terms: inverse_cdf_sample(target_probs(logits[r], T, dtype, top_k, top_p), u[r]).  u[r] lies in [0, 1); ids without mass
+ * (-inf logits, filtered ids) are never drawn.  Rows holding NaN / +inf keep the plain float32 formula, as in the other draws.
+ * A row's token depends on that row's logits, record and uniform alone.  Four launches whatever R is (row selection, the two
+ * row-sum launches over R * 16 workgroups, one pick workgroup per row); no workgroup waits for another.
+ *   workspace: jf_rs_draw_workspace_bytes(R) bytes (= jf_rs_step_workspace_bytes(R)), 16-byte aligned.
+ */
+JF_API size_t jf_rs_draw_workspace_bytes(int64_t R);
+JF_API int jf_rs_draw_rows(const void *logits, int dtype, int64_t R, int64_t V, int64_t row_stride,
+                    const float *row_max, const float *row_sumexp, float temperature,
+                    const jf_rs_filter_row *filt /* nullable: jf_rs_filter's records of the R rows */,
+                    const float *u /* [R] */, int64_t *tokens /* [R] out */,
+                    void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,8 @@ _SIGNATURES = {
                                       _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "jf_rs_onpolicy_step_batch": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_float,
                                             _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "jf_rs_draw_workspace_bytes": (_sz, [_i64]),
+    "jf_rs_draw_rows": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

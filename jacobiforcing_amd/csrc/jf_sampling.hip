@@ -4340,6 +4340,67 @@ extern "C" int jf_rs_onpolicy_step_batch(const void *logits, int dtype, int64_t 
                         n_stop, committed, redraft, rows, workspace, filt, stream, "rs_onpolicy batch kernels");
 }
 
+// ------------------------------------------------------------------------------------------------
+// One token per row from one uniform per row (the autoregressive sampler): the inverse-CDF draw of the bonus / re-draft
+// draws without an accept walk in front of it, so nothing is avoided and no stream has a cursor.
+//   rs_draw_select_kernel   every row asks for its sums (sel_row = its own index, avoid = none)
+//   rs_rowsum_a/b           (R * RS_SEG) float64 sums and exact CDF sums of every row (above)
+//   rs_draw_pick_kernel     one workgroup per row: ONE walk at u[r]
+// Four launches whatever R is; a row's token depends on that row's logits, its record and its uniform alone.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rs_draw_select_kernel(int R, RsWs w) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < R) { w.sel_row[i] = i; w.avoid[i] = -1; }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void rs_draw_pick_kernel(const void *logits, int64_t V, int64_t row_stride, const float *row_max,
+                                                            const float *row_sumexp, float temp, RsWs w, const float *u,
+                                                            int64_t *tokens) {
+    __shared__ RsPickShared sh;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    rs_load_tab(sh.tab);
+    __syncthreads();
+    const RsRow row = rs_step_row<DT>(logits, r, V, row_stride, temp, row_max, row_sumexp, w.filt);
+    const float ur = u[r];
+    int y;
+    if (rs_hier_ok(V, Elem<DT>::EPV)) {
+        if (tid < 64) { const int yy = rs_pick_wave<DT, false>(row, w, r, w.s64[r], ur, sh.tab, tid); if (tid == 0) sh.pick = yy; }
+        __syncthreads();
+        y = sh.pick;
+    } else {
+        y = rs_pick_wg<DT>(row, w.segsum + (int64_t)r * RS_SEG, w.s64[r], ur, sh);
+    }
+    if (tid == 0) tokens[r] = y;
+}
+
+extern "C" size_t jf_rs_draw_workspace_bytes(int64_t R) { return jf_rs_step_workspace_bytes(R); }
+
+extern "C" int jf_rs_draw_rows(const void *logits, int dtype, int64_t R, int64_t V, int64_t row_stride, const float *row_max,
+                               const float *row_sumexp, float temperature, const jf_rs_filter_row *filt, const float *u,
+                               int64_t *tokens, void *workspace, size_t workspace_bytes, void *stream) {
+    if (R <= 0) return JF_OK;
+    if (!logits || !row_max || !row_sumexp || !u || !tokens || !workspace) return fail(JF_E_INVALID, "jf_rs_draw_rows: null pointer");
+    if (dtype != JF_F32 && dtype != JF_BF16) return fail(JF_E_INVALID, "jf_rs_draw_rows: dtype %d", dtype);
+    if (V <= 0 || V > 0x7FFFFFFFll) return fail(JF_E_INVALID, "jf_rs_draw_rows: V=%lld", (long long)V);
+    if (R * RS_SEG > 0x7FFFFFFFll) return fail(JF_E_INVALID, "jf_rs_draw_rows: R=%lld", (long long)R);
+    if (workspace_bytes < rs_ws_bytes(R) || ((uintptr_t)workspace % 16) != 0) return fail(JF_E_INVALID, "jf_rs_draw_rows: workspace too small or not 16-byte aligned");
+    float t = (temperature <= 0.f) ? 1.f : temperature;
+    if (dtype == JF_BF16 && t != 1.f && rs_scale_is_exact(t)) t = -t;    // the kernels' rows take the product form of the scaling (rs_make_row)
+    hipStream_t s = (hipStream_t)stream;
+    RsWs w = rs_ws(workspace, R);
+    w.filt = filt;
+    const unsigned nseg = (unsigned)(R * RS_SEG), nrow = (unsigned)R;
+    rs_draw_select_kernel<<<(nrow + 255) / 256, 256, 0, s>>>((int)R, w);
+#define JF_DRAW(DT)                                                                                                  \
+    rs_rowsum_a_kernel<DT><<<nseg, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                    \
+    rs_rowsum_b_kernel<DT><<<nseg, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w);                    \
+    rs_draw_pick_kernel<DT><<<nrow, 256, 0, s>>>(logits, V, row_stride, row_max, row_sumexp, t, w, u, tokens)
+    if (dtype == JF_F32) { JF_DRAW(JF_F32); } else { JF_DRAW(JF_BF16); }
+#undef JF_DRAW
+    return check_launch("rs_draw kernels");
+}
+
 // May the one-launch step run on this device?  Its three role workgroups and the workgroups of two rows (a row's wait for each
 // other) must fit at once in HALF of what the runtime says it keeps resident; everything else only waits backwards
 // in dispatch order.

@@ -211,6 +211,7 @@ class ModelRunner:
         self.block_manager = None
         self.jacobi_decoder = None
         self._mb_decoders = {}
+        self._ar_sampler = None                                   # ops.ARSampler, built at the first seeded autoregressive draw
         self.profiler = ProfileTimer(self.device)
         self._kv_host = [0] * self.max_rows
         self._logit_idx = {}
@@ -481,10 +482,12 @@ class ModelRunner:
         temps = [float(seq.temperature) for seq in seqs]
         if all(t == 0.0 for t in temps):
             return [int(t) for t in ops.argmax_rows(logits).cpu().tolist()]
-        toks = []
+        toks = self._ar_sample_seeded(seqs, temps, logits)      # the rows of the batched HIP sampler (None: a row of the loop below)
         for i, t in enumerate(temps):
+            if toks[i] is not None:
+                continue
             if t == 0.0:
-                toks.append(int(ops.argmax_rows(logits[i:i + 1])[0]))
+                toks[i] = int(ops.argmax_rows(logits[i:i + 1])[0])
             else:                                               # Gumbel-max sampling like layers/sampler.py:10-24
                 p = torch.softmax(logits[i:i + 1].float() / t, dim=-1)
                 # top_k / top_p planted on the request (the Jacobi decoders read them the same way, JDN:117-118): the same target
@@ -500,7 +503,42 @@ class ModelRunner:
                     keep[..., 0] = True                         # at least the most likely token
                     sp = sp * keep
                     p = torch.zeros_like(p).scatter_(-1, si, sp / sp.sum(dim=-1, keepdim=True).clamp_min(1e-12))
-                toks.append(int(torch.argmax(p / torch.empty_like(p).exponential_(1).clamp_min_(1e-10), dim=-1)[0]))
+                toks[i] = int(torch.argmax(p / torch.empty_like(p).exponential_(1).clamp_min_(1e-10), dim=-1)[0])
+        return toks
+
+    def _ar_sample_seeded(self, seqs: List[Sequence], temps: List[float], logits: torch.Tensor) -> list:
+        """Tokens of the rows that ``ops.ARSampler`` samples, None for every other row.  A request with ``temperature > 0`` goes
+        there when its SamplingParams carries a planted integer ``seed`` (read with getattr like top_k / top_p: no such field
+        upstream), or when JF_AR_SAMPLER=1 — its seed is then drawn once from torch's global generator at its first draw and kept
+        on the request.  The uniform of its j-th completion token is ``ops.ar_stream(seed, j, 1)``, j = seq.num_completion_tokens:
+        a function of the request alone, whatever shares the batch.  Greedy rows of such a step ride along (one argmax launch for
+        all of them).  Without a seed and without the variable nothing here touches the library or the generator."""
+        toks: list = [None] * len(seqs)
+        opt_in = os.environ.get("JF_AR_SAMPLER", "0") == "1"
+        seeds = {}
+        for i, (seq, t) in enumerate(zip(seqs, temps)):
+            if t == 0.0:
+                continue
+            seed = getattr(getattr(seq, "sampling_params", None), "seed", None)
+            if seed is None and opt_in:
+                seed = getattr(seq, "_ar_seed", None)
+                if seed is None:
+                    seed = seq._ar_seed = int(torch.randint(0, 1 << 62, (1,)).item())
+            if seed is not None:
+                seeds[i] = int(seed)
+        if not seeds:
+            return toks
+        if self._ar_sampler is None:
+            self._ar_sampler = ops.ARSampler(self.device, self.max_rows)
+        smp = self._ar_sampler
+        rows = [i for i, t in enumerate(temps) if t == 0.0 or i in seeds]
+        V = logits.shape[-1]
+        settings = [(0.0, 0, 0.0) if temps[i] == 0.0 else (temps[i],) + ops.active_filters(getattr(seqs[i], "sampling_params", None), V)
+                    for i in rows]
+        u = [smp.uniform(seeds[i], seqs[i].num_completion_tokens) if i in seeds else 0.0 for i in rows]
+        sub = logits if len(rows) == len(seqs) else logits.index_select(0, torch.tensor(rows, dtype=torch.int64, device=logits.device))
+        for i, tok in zip(rows, smp.sample(sub, settings, u)):
+            toks[i] = tok
         return toks
 
     # ------------------------------------------------------------------------------------------ MR:1464-1550

@@ -1373,3 +1373,134 @@ class OnPolicyBatchStepper(_OnPolicyCore):
             out_cm.append(host[g * Lm:g * Lm + row["n_committed"]].tolist())
             out_rd.append(host[n + g * Lm:n + g * Lm + int(n_rows[g])].tolist())
         return out_rows, out_cm, out_rd
+
+
+# --------------------------------------------------------------------------------------------
+# autoregressive sampler: one token per row from one uniform per row (jf_rs_draw_rows)
+# --------------------------------------------------------------------------------------------
+AR_STREAM_BLOCK = 256             # uniforms generated per (seed, block) and cached by ARSampler
+
+
+def ar_stream(seed: int, start: int, count: int) -> np.ndarray:
+    """Uniforms ``start .. start + count - 1`` of the counter-based stream of ``seed``, float32 [count].
+
+    The construction, for a caller that wants to inject or reproduce the draws of a request: with
+    ``raw = numpy.random.Philox(key=seed mod 2**64).random_raw(n)`` (Philox-4x64-10, counter 0: four 64-bit words per counter
+    value, in order), uniform ``j`` is ``(raw[j] >> 40) * 2**-24`` — the top 24 bits of word ``j``, a multiple of 2**-24 in
+    [0, 1) that a float32 holds exactly.  It is a pure function of ``(seed, j)``: any window is generated from the counter
+    ``j // 4`` onwards, whatever was asked before.  A request's ``j``-th completion token (``j = seq.num_completion_tokens``
+    at the draw, prefill's first token is ``j = 0``) is ``inverse_cdf(p, ar_stream(seed, j, 1)[0])`` with ``p`` the request's
+    target distribution — independent of the batch it is decoded in, and unchanged by pre-emption."""
+    start, count = int(start), int(count)
+    if start < 0 or count < 0:
+        raise ValueError("ar_stream: start and count must be non-negative")
+    skip = start % 4
+    bg = np.random.Philox(key=int(seed) % (1 << 64), counter=start // 4)
+    raw = bg.random_raw(skip + count)[skip:] if count else np.zeros((0,), dtype=np.uint64)
+    return ((raw >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+
+
+class ARSampler:
+    """The sampling part of an autoregressive decode step for rows with their own settings: per group of rows that share
+    ``(temperature, top_k, top_p)`` jf_rs_probs -> [jf_rs_filter] -> jf_rs_draw_rows (greedy rows: one ``argmax_rows``), all
+    tokens of the step in one device tensor, one pinned read-back and one synchronise per step however many groups there are.
+    A batch that mixes settings is decoded setting by setting, as everywhere in this package; a batch with one setting reads
+    the logits where they are."""
+
+    def __init__(self, device, max_rows: int = 64):
+        dev = torch.device(device)
+        self.device = dev
+        self.filter: Optional[RowFilter] = None
+        self._blocks: dict = {}                                           # (seed, block) -> AR_STREAM_BLOCK uniforms
+        self._ws_need: dict = {}
+        self.ws = torch.zeros((16,), dtype=torch.float32, device=dev)     # grown to jf_rs_workspace_bytes(R, V) on demand
+        self.draw_ws = torch.zeros((2,), dtype=torch.float64, device=dev)
+        self._alloc(int(max_rows))
+
+    def _alloc(self, n: int) -> None:
+        dev, pin = self.device, self.device.type == "cuda"
+        self.rows = n
+        self.packed = new_packed(n, dev)                                  # jf_rs_probs' argmax slots: never read here, so never re-zeroed
+        f32 = lambda: torch.zeros((n,), dtype=torch.float32, device=dev)
+        self.p_draft, self.row_max, self.row_sumexp, self.u = f32(), f32(), f32(), f32()
+        self.draft_next = torch.zeros((n,), dtype=torch.int64, device=dev)
+        self.tokens = torch.zeros((n,), dtype=torch.int64, device=dev)
+        self.u_host = torch.zeros((n,), dtype=torch.float32, pin_memory=pin)
+        self.tok_host = torch.zeros((n,), dtype=torch.int64, pin_memory=pin)
+        self.draw_ws = _grown(self.draw_ws, int(N.lib().jf_rs_draw_workspace_bytes(n)) + 16)
+
+    # ---- the per-request streams ----------------------------------------------------------------
+    def uniform(self, seed: int, j: int) -> float:
+        """``ar_stream(seed, j, 1)[0]`` through a cache of whole blocks (a request asks for j, j + 1, ... in turn)."""
+        key = (int(seed), int(j) // AR_STREAM_BLOCK)
+        blk = self._blocks.get(key)
+        if blk is None:
+            if len(self._blocks) >= 4096:
+                self._blocks.clear()
+            blk = self._blocks[key] = ar_stream(key[0], key[1] * AR_STREAM_BLOCK, AR_STREAM_BLOCK)
+        return blk[int(j) % AR_STREAM_BLOCK]
+
+    # ---- one decode step --------------------------------------------------------------------------
+    def _draw(self, flat: torch.Tensor, setting, u: torch.Tensor, out: torch.Tensor) -> None:
+        """jf_rs_probs -> [jf_rs_filter] -> jf_rs_draw_rows on the rows of one setting."""
+        temperature, top_k, top_p = setting
+        R, V = flat.shape
+        dev, lib, dt = self.device, N.lib(), _dtype_code(flat)
+        stride = flat.stride(0) if R > 1 else V
+        need = self._ws_need.get((R, V))
+        if need is None:
+            need = self._ws_need[(R, V)] = int(lib.jf_rs_workspace_bytes(R, V))
+        self.ws = _grown(self.ws, need)
+        N.check(lib.jf_rs_probs(_ptr(flat), dt, R, V, stride, _ptr(self.draft_next), float(temperature), _ptr(self.p_draft),
+                                _ptr(self.row_max), _ptr(self.row_sumexp), _ptr(self.packed), _ptr(self.ws), self.ws.numel() * 4,
+                                _stream(dev)), "jf_rs_probs")
+        filt = None
+        if int(top_k) > 0 or float(top_p) > 0.0:
+            if self.filter is None:
+                self.filter = RowFilter(dev)
+            filt = self.filter.run(flat, self.draft_next[:R], temperature, top_k, top_p, self.p_draft, self.row_max, self.row_sumexp)
+        N.check(lib.jf_rs_draw_rows(_ptr(flat), dt, R, V, stride, _ptr(self.row_max), _ptr(self.row_sumexp), float(temperature),
+                                    _ptr(filt), _ptr(u), _ptr(out), _ptr(self.draw_ws), self.draw_ws.numel() * 8, _stream(dev)),
+                "jf_rs_draw_rows")
+
+    def sample(self, logits: torch.Tensor, settings: Sequence[Tuple[float, int, float]], u) -> List[int]:
+        """logits [B, V] on the device; settings[b] = (temperature, top_k, top_p) with the filters as ``active_filters`` gives
+        them (0 / 0.0: off; temperature 0: greedy, its uniform is ignored); u [B] host floats in [0, 1) -> the B token ids."""
+        if logits.dim() != 2 or logits.shape[0] != len(settings):
+            raise ValueError(f"logits must be [B, V] with one setting per row, got {tuple(logits.shape)} for {len(settings)} settings")
+        B, V = logits.shape
+        if B == 0:
+            return []
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        if B > self.rows:
+            self._alloc(max(B, 2 * self.rows))
+        dev = self.device
+        groups: dict = {}
+        for b, s in enumerate(settings):
+            t = float(s[0])
+            groups.setdefault((0.0, 0, 0.0) if t == 0.0 else (t, int(s[1]), float(s[2])), []).append(b)
+        order = [b for rows in groups.values() for b in rows]            # the step's rows, setting by setting
+        self.u_host[:B].copy_(torch.from_numpy(np.asarray(u, dtype=np.float32).reshape(B)[order]))
+        self.u[:B].copy_(self.u_host[:B], non_blocking=True)
+        a = 0
+        for setting, rows in groups.items():
+            n = len(rows)
+            if rows == list(range(rows[0], rows[0] + n)):                 # (one setting: the logits as they are)
+                sub = logits[rows[0]:rows[0] + n]
+            else:
+                sub = logits.index_select(0, torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True))
+            out = self.tokens[a:a + n]
+            if setting[0] == 0.0:
+                out.copy_(argmax_rows(sub))
+            else:
+                self._draw(sub, setting, self.u[a:a + n], out)
+            a += n
+        self.tok_host[:B].copy_(self.tokens[:B], non_blocking=True)
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()
+        got = self.tok_host[:B].tolist()
+        toks = [0] * B
+        for k, b in enumerate(order):
+            toks[b] = int(got[k])
+        return toks
