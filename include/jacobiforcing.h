@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 /* 600 also covers the entry points added after it (the forward glue: jf_attn_out_relayout, jf_forward_plan; the autoregressive
- * sampler: jf_rs_draw_workspace_bytes, jf_rs_draw_rows): additions only, every earlier signature is unchanged.  A client that
+ * sampler: jf_rs_draw_workspace_bytes, jf_rs_draw_rows; log-probabilities: jf_logprobs_workspace_bytes, jf_logprobs_rows): additions only, every earlier signature is unchanged.  A client that
  * needs them checks for the symbols (dlsym), not for a version. */
 #define JF_VERSION 600
 
@@ -670,6 +670,36 @@ JF_API int jf_rs_draw_rows(const void *logits, int dtype, int64_t R, int64_t V, 
                     const jf_rs_filter_row *filt /* nullable: jf_rs_filter's records of the R rows */,
                     const float *u /* [R] */, int64_t *tokens /* [R] out */,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-token log-probabilities (ops.LogprobRows): for every row r of logits [R, V] the log-probability and the rank of the
+ * id chosen[r], and the row's top_n most likely ids with their log-probabilities.  xs is the scaled row exactly as defined
+ * above for every jf_rs_* call (JF_F32: fl32(x / T); JF_BF16: bf16(float(x) / float(T)); T == 1 leaves x as it is, T <= 0 is
+ * treated as 1; a true division).  With m = max xs and S = sum exp(xs - m):
+ *   logprob(id) = (xs[id] - m) - ln S, as float32: the log of the UNROUNDED softmax at the request's temperature.  top_k /
+ *                 top_p are NOT applied: it is the model's distribution, not the truncated distribution a token was drawn from.
+ *                 The partial sums are float32 per chunk and merged in float64, so the error is the documented one of a float32
+ *                 row sum (~4e-5 + 3.5e-7 |m|) plus one float32 rounding of the result.
+ *   order       of a row's ids: descending xs, equal xs (-0.0 == +0.0) by ascending id; exact (no arithmetic beyond the scaling).
+ *   rank[r]     = 1 + the number of ids in front of chosen[r] in this order.
+ *   top_ids[r, 0..top_n) = the first top_n ids of the order, top_logprobs[r, :] their log-probabilities; when V < top_n the
+ *                 remaining slots hold id -1 and -inf.
+ * A row without a finite maximum, or holding NaN or +inf (in xs): every log-probability of the row is NaN, its rank -1 and
+ * its top ids -1; other rows of the call are unaffected.  A chosen id outside [0, V) gives logprob NaN and rank -1 and is never
+ * dereferenced (the rollout steppers pass their device `committed` array, whose tail is stale).
+ * The call computes its own row statistics (jf_rs_filter overwrites jf_rs_probs' with markers and the greedy paths have none):
+ * two launches whatever R is — one workgroup per (row, chunk of 256 * 8 vectors), then one per row; no atomics, no workgroup
+ * waits for another.  A row's outputs depend on that row alone.
+ *   workspace: jf_logprobs_workspace_bytes(R, V, top_n) bytes (enough for either dtype), 16-byte aligned.
+ *   top_n in 0..JF_LOGPROBS_MAX_TOP; top_ids / top_logprobs may be null iff top_n == 0.  R == 0 returns JF_OK without a launch.
+ */
+#define JF_LOGPROBS_MAX_TOP 20
+JF_API size_t jf_logprobs_workspace_bytes(int64_t R, int64_t V, int32_t top_n);
+JF_API int jf_logprobs_rows(const void *logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float temperature,
+                            const int64_t *chosen /* [R] */, int32_t top_n /* 0..JF_LOGPROBS_MAX_TOP */,
+                            float *logprob /* [R] */, int32_t *rank /* [R] */,
+                            int64_t *top_ids /* [R, top_n], null iff top_n == 0 */, float *top_logprobs /* [R, top_n] */,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -172,7 +172,10 @@ _SIGNATURES = {
                                             _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "jf_rs_draw_workspace_bytes": (_sz, [_i64]),
     "jf_rs_draw_rows": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "jf_logprobs_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "jf_logprobs_rows": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
+LOGPROBS_MAX_TOP = 20            # JF_LOGPROBS_MAX_TOP
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _LIB = None

@@ -9,6 +9,7 @@
 //   jf_kv.hip         (a18) KV append, fused RoPE + append, SwiGLU, attention-output re-layout, forward plan; (a9/a10) KV commit
 //   jf_engine.hip     (a15) engine single-block step, (a16) paged-KV index fill
 //   jf_sampling.hip   (a19) non-greedy verify (jf_rs_probs, jf_rs_step) and the on-policy rollout step
+//   jf_logprobs.hip   per-token log-probabilities, rank and top N (jf_logprobs_rows)
 #ifndef JF_COMMON_H
 #define JF_COMMON_H
 

@@ -5,7 +5,11 @@ OUTPUT FORMAT (JDO:7-28): ``generate_rollout_records_batch(seqs)`` returns one d
 each block record holds ``diffusion_itr_id`` ("itr_k"), ``data_id``, ``prompt_ids`` (prefix before the block, left padding
 trimmed), ``answer_trajectory_ids`` (block-local trajectory: one fixed-length vector per forward = accepted prefix + current
 drafted suffix), ``teacher_output_ids`` (final prompt + completion, stop-truncated, filled in for ALL blocks at the end) and
-the cumulative ``tokens_per_iter / tokens_per_forward / num_iters / num_forwards``.
+the cumulative ``tokens_per_iter / tokens_per_forward / num_iters / num_forwards``.  Beyond the reference: a request whose
+SamplingParams carries a planted ``logprobs`` (0..20) also gets ``answer_logprobs`` — one float per token the block appended
+and kept, the log-probability of that token under the model's distribution at the request's temperature (top_k / top_p not
+applied; ``jf_logprobs_rows`` queued behind the step on the same rows) — and, above 0, ``answer_top_logprobs``: per token the N
+most likely ``(id, log-probability)`` pairs.  Records of requests that do not ask are unchanged.
 
 Per forward the verify (accept iff u < p, bonus != proposed on the first rejection, stop-token set; JDO:270-327) and the
 fresh multinomial sample of every not yet accepted position (JDO:465-477) run on the GPU: ``jf_rs_probs`` reads the logits
@@ -81,6 +85,8 @@ class _BlockState:
         self.accepted = 0
         self.stopped = False
         self.trajectory: List[List[int]] = []
+        self.logprobs: List[float] = []          # one per token this block appended and kept (requests that asked for them)
+        self.top_logprobs: List[list] = []
 
     def start(self, init: List[int]) -> None:
         self.tokens = list(init) + [self.pad] * (self.full_len - self.gen_len)
@@ -147,6 +153,7 @@ class JacobiDecoderNonGreedyOnPolicy:
         self._batch_stepper: Optional[ops.OnPolicyBatchStepper] = None
         self.max_forward_positions: Optional[int] = None      # positions the caller's cache holds per sequence (None: no bound)
         self.lockstep_forwards: List[Tuple[int, int, int]] = []   # (rows, padded length, valid rows) of the last lock-step call's forwards
+        self._logprob_rows: Optional[ops.LogprobRows] = None       # built when the first request asks for log-probabilities
 
     # ------------------------------------------------------------------------------- randomness
     def set_streams(self, rnd, uniforms, multinomial) -> None:
@@ -227,6 +234,21 @@ class JacobiDecoderNonGreedyOnPolicy:
         return (temperature,) + ops.active_filters(sp, self.vocab_size)
 
     @staticmethod
+    def _logprobs_of(seq: Sequence) -> Optional[int]:
+        """The planted ``logprobs`` of the request (None: it does not ask; 0: the tokens' log-probabilities; 1..20: the top N too)."""
+        n = getattr(getattr(seq, "sampling_params", None), "logprobs", None)
+        if n is None:
+            return None
+        if not 0 <= int(n) <= 20:
+            raise ValueError(f"logprobs must lie in 0..20, got {n}")
+        return int(n)
+
+    def _logprob_rows_for(self, rows: int) -> "ops.LogprobRows":
+        if self._logprob_rows is None:
+            self._logprob_rows = ops.LogprobRows(self.device, max(int(rows), 64))
+        return self._logprob_rows
+
+    @staticmethod
     def _check_vocab(proposed, V: int) -> None:
         """JDO:298-301"""
         bad = next((x for x in proposed if not 0 <= x < V), None)
@@ -235,16 +257,24 @@ class JacobiDecoderNonGreedyOnPolicy:
                              "This may indicate a mismatch between model vocab and tokenizer vocab.")
 
     def _commit_row(self, seq: Sequence, blk: _BlockState, proposed: List[int], row: dict, committed: List[int],
-                    redraft: List[int], cursors: List[int], cached_positions: int, completion_start_len: int) -> int:
+                    redraft: List[int], cursors: List[int], cached_positions: int, completion_start_len: int,
+                    lps=None, top_n: int = 0) -> int:
         """What one step's record does to its sequence and block (JDO:412-477); ``cursors``: the [uniforms, multinomial] draw
-        counts to advance; ``cached_positions``: how many positions behind the seed the forward cached.  Returns the number
-        of tokens appended."""
+        counts to advance; ``cached_positions``: how many positions behind the seed the forward cached.  ``lps``: the step's
+        (logprobs, top_ids, top_logprobs) of the row when the request asked for them (row t: committed[t]); the block keeps one
+        entry per token it appended and kept.  Returns the number of tokens appended."""
         bm = self.block_manager
         cursors[0] += row["n_uniforms"]
         cursors[1] += row["n_bonus_draws"] + row["n_redraft"]
         stop_hit = bool(row["stop_hit"])
+        if lps is not None:
+            blk.logprobs += [float(x) for x in lps[0][:len(committed)]]
+            blk.top_logprobs += [[(int(a), float(b)) for a, b in zip(lps[1][t, :top_n], lps[2][t, :top_n])] for t in range(len(committed))]
         if not committed:
             committed, stop_hit = [proposed[0]], proposed[0] in blk.stop
+            if lps is not None:                                                     # (the kernels always commit at least one token)
+                blk.logprobs.append(float("nan"))
+                blk.top_logprobs.append([(-1, float("nan"))] * top_n)
         seq.extend_tokens(committed)                                                # JDO:412-416
         if bm is not None:
             bm.may_append_batch(seq, len(committed))
@@ -261,6 +291,8 @@ class JacobiDecoderNonGreedyOnPolicy:
                 seq.token_ids = kept
                 if bm is not None:
                     bm.trim_kv_only_fast(seq, dropped)
+                if lps is not None:                                                  # truncated together with the tokens
+                    del blk.logprobs[len(blk.logprobs) - dropped:], blk.top_logprobs[len(blk.top_logprobs) - dropped:]
             blk.close_at_stop(first_new)
         elif blk.accepted < blk.gen_len:                                             # JDO:465-477 (samples drawn on the GPU)
             blk.refill(redraft[len(committed):])
@@ -270,15 +302,17 @@ class JacobiDecoderNonGreedyOnPolicy:
     # ------------------------------------------------------------------------------- one block (JDO:331-488)
     @torch.inference_mode()
     def _run_one_block(self, seq: Sequence, block_len: int, token_budget_remaining: int,
-                       completion_start_len: int) -> Tuple[List[List[int]], int, int, bool]:
-        """Returns (trajectory, tokens appended, forwards used, stopped)."""
+                       completion_start_len: int) -> Tuple[List[List[int]], int, int, bool, Optional[_BlockState]]:
+        """Returns (trajectory, tokens appended, forwards used, stopped, the block's state)."""
         if int(block_len) <= 0 or token_budget_remaining <= 0:
-            return [], 0, 0, True
+            return [], 0, 0, True, None
         blk = _BlockState(int(block_len), min(int(block_len), int(token_budget_remaining)), self.pad_token_id,
                           self.stop_token_ids)
         blk.start(self._init_block_draft_from_prompt(list(seq.token_ids), blk.gen_len))
         temperature, top_k, top_p = self._sampling_of(seq)
         st = self._ensure(blk.full_len + 1)
+        top_n = self._logprobs_of(seq)
+        lp_kw = {} if top_n is None else dict(logprobs=self._logprob_rows_for(st.max_L), top_n=top_n)
         fwd_used = appended_total = 0
         while blk.open():
             if not seq.token_ids:
@@ -292,10 +326,10 @@ class JacobiDecoderNonGreedyOnPolicy:
             if logits.ndim != 3 or int(logits.size(0)) != 1 or int(logits.size(1)) != remaining:
                 raise ValueError(f"forward must return logits [1, {remaining}, vocab], got {tuple(logits.shape)}")
             self._check_vocab(proposed, int(logits.size(-1)))
-            row, committed, redraft = st.step(draft[0, 1:], logits[0], temperature, self._cur, top_k, top_p)
+            row, committed, redraft, *lps = st.step(draft[0, 1:], logits[0], temperature, self._cur, top_k, top_p, **lp_kw)
             appended_total += self._commit_row(seq, blk, proposed, row, committed, redraft, self._cur, remaining,
-                                               completion_start_len)
-        return blk.trajectory, appended_total, fwd_used, blk.stopped
+                                               completion_start_len, lps[0] if lps else None, top_n or 0)
+        return blk.trajectory, appended_total, fwd_used, blk.stopped, blk
 
     # ------------------------------------------------------------------------------- one block round, all sequences together
     def _lockstep_groups(self, seqs: List[Sequence], rows: List[int], blocks: Dict[int, _BlockState]) -> List[List[int]]:
@@ -320,8 +354,8 @@ class JacobiDecoderNonGreedyOnPolicy:
 
     @torch.inference_mode()
     def _run_blocks_lockstep(self, seqs: List[Sequence], rows: List[int], block_lens: List[int], budgets: List[int],
-                             completion_start_lens: List[int]) -> Dict[int, Tuple[List[List[int]], int, int, bool]]:
-        """``_run_one_block`` for the sequences ``rows`` of the batch at once: {i: (trajectory, appended, forwards, stopped)}."""
+                             completion_start_lens: List[int]) -> Dict[int, Tuple[List[List[int]], int, int, bool, _BlockState]]:
+        """``_run_one_block`` for the sequences ``rows`` of the batch at once: {i: (trajectory, appended, forwards, stopped, block)}."""
         if not rows:
             return {}
         st = self._ensure_batch(len(seqs), max(int(block_lens[i]) for i in rows) + 1)
@@ -329,6 +363,7 @@ class JacobiDecoderNonGreedyOnPolicy:
         pad = self.pad_token_id
         blocks: Dict[int, _BlockState] = {}
         fwd_used, appended = {i: 0 for i in rows}, {i: 0 for i in rows}
+        asks = {i: self._logprobs_of(seqs[i]) for i in rows}
         for i in rows:                                                               # every block opens from the round's start state
             blk = _BlockState(int(block_lens[i]), min(int(block_lens[i]), int(budgets[i])), pad, self.stop_token_ids)
             blk.start(self._init_block_draft_from_prompt(list(seqs[i].token_ids), blk.gen_len, rnds[i]))
@@ -355,12 +390,15 @@ class JacobiDecoderNonGreedyOnPolicy:
                     raise ValueError(f"forward must return logits [{len(group)}, {Lm}, vocab], got {tuple(logits.shape)}")
                 self._check_vocab((x for p in proposed for x in p), int(logits.size(-1)))
                 temperature, top_k, top_p = self._sampling_of(gs[0])
-                recs, committed_all, redraft_all = st.step(draft[:, 1:], n_rows, logits, temperature, group, top_k, top_p)
-                for i, seq, prop, row, committed, redraft in zip(group, gs, proposed, recs, committed_all, redraft_all):
+                want = [asks[i] for i in group if asks[i] is not None]           # one launch pair for the group's rows if any of them asks
+                lp_kw = dict(logprobs=self._logprob_rows_for(len(group) * Lm), top_n=max(want)) if want else {}
+                recs, committed_all, redraft_all, *lps = st.step(draft[:, 1:], n_rows, logits, temperature, group, top_k, top_p, **lp_kw)
+                for g, (i, seq, prop, row, committed, redraft) in enumerate(zip(group, gs, proposed, recs, committed_all, redraft_all)):
                     fwd_used[i] += 1
                     appended[i] += self._commit_row(seq, blocks[i], prop, row, committed, redraft, self.cursors_per_sequence[i],
-                                                    Lm, completion_start_lens[i])   # the forward cached Lm positions behind the seed
-        return {i: (blocks[i].trajectory, appended[i], fwd_used[i], blocks[i].stopped) for i in rows}
+                                                    Lm, completion_start_lens[i],   # the forward cached Lm positions behind the seed
+                                                    lps[0][g] if lps and asks[i] is not None else None, asks[i] or 0)
+        return {i: (blocks[i].trajectory, appended[i], fwd_used[i], blocks[i].stopped, blocks[i]) for i in rows}
 
     # ------------------------------------------------------------------------------- records (JDO:494-614)
     @torch.inference_mode()
@@ -400,11 +438,11 @@ class JacobiDecoderNonGreedyOnPolicy:
                     continue
                 if round_out is not None:
                     prompt_ids_trim = prompts_trim[i]
-                    traj, appended_now, fwd_used, stop_hit = round_out[i]
+                    traj, appended_now, fwd_used, stop_hit, blk = round_out[i]
                 else:
                     prompt_ids_trim = _trim_left_padding(list(seq.token_ids), self.pad_token_id)
-                    traj, appended_now, fwd_used, stop_hit = self._run_one_block(seq, block_lens[i], budgets[i],
-                                                                                 completion_start_lens[i])
+                    traj, appended_now, fwd_used, stop_hit, blk = self._run_one_block(seq, block_lens[i], budgets[i],
+                                                                                      completion_start_lens[i])
                 num_blocks_done[i] += 1
                 num_forwards[i] += int(fwd_used)
                 total_generated[i] += int(appended_now)
@@ -419,6 +457,11 @@ class JacobiDecoderNonGreedyOnPolicy:
                     "tokens_per_forward": tok / float(max(1, num_forwards[i])),
                     "num_iters": int(num_blocks_done[i]), "num_forwards": int(num_forwards[i]),
                 }
+                top_n = self._logprobs_of(seq)
+                if top_n is not None:                # the request asked: one entry per token this block appended and kept
+                    per_seq_out[i][k]["answer_logprobs"] = list(blk.logprobs) if blk is not None else []
+                    if top_n > 0:
+                        per_seq_out[i][k]["answer_top_logprobs"] = list(blk.top_logprobs) if blk is not None else []
         final_teacher_by_id: Dict[str, List[int]] = {}
         for i in range(B):
             full = _truncate_after_stop(list(seqs[i].token_ids), completion_start_lens[i], self.stop_token_ids)

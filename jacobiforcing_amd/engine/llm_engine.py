@@ -1,8 +1,10 @@
 """``LLMEngine`` — request plumbing with the reference's surface (inference_engine/engine/llm_engine.py:15-202):
-``add_request``, ``step``, ``is_finished``, ``generate`` returning ``[{"text", "token_ids"}]``, ``exit``."""
+``add_request``, ``step``, ``is_finished``, ``generate`` returning ``[{"text", "token_ids"}]``, ``exit``.  A request whose
+SamplingParams carries a planted ``logprobs`` (0..20) also gets ``"logprobs"``, ``"ranks"`` and, above 0, ``"top_logprobs"``."""
 from __future__ import annotations
 
 import atexit
+import copy
 import sys
 from dataclasses import fields
 from time import perf_counter
@@ -20,6 +22,7 @@ class LLMEngine:
         config = Config(model, **{k: v for k, v in kwargs.items() if k in config_fields})       # ENG:20-22
         self.config = config
         self.ps, self.events, self._exited = [], [], False
+        self._logprob_outputs = {}                                 # seq_id -> the extra output keys of a finished request that asked
         self.model_runner = ModelRunner(config, 0, self.events, device=kwargs.get("device"))
         self.tokenizer = None
         tok_path = tokenizer_path or model
@@ -84,13 +87,40 @@ class LLMEngine:
         for seq in seqs:
             if seq.is_finished:
                 outputs.append((seq.seq_id, seq.completion_token_ids))
+                n_top = getattr(getattr(seq, "sampling_params", None), "logprobs", None)
+                if n_top is not None:                              # the request asked for log-probabilities (ModelRunner._ar_logprobs)
+                    n = seq.num_completion_tokens
+                    extra = {"logprobs": list(getattr(seq, "_logprobs", []))[:n], "ranks": list(getattr(seq, "_ranks", []))[:n]}
+                    if int(n_top) > 0:
+                        extra["top_logprobs"] = list(getattr(seq, "_top_logprobs", []))[:n]
+                    self._logprob_outputs[seq.seq_id] = extra
                 self.model_runner.release(seq)
         return outputs, (sum(len(seq) for seq in seqs) if is_prefill else -num_new)
 
     def is_finished(self):
         return self.scheduler.is_finished()
 
-    def generate(self, prompts, sampling_params, use_tqdm: bool = True):
+    def generate(self, prompts, sampling_params, use_tqdm: bool = True, logprobs=None):
+        """``logprobs`` (not in the reference): an int asks for every request, a list gives one value per prompt (None: that
+        request does not ask); it is planted on a copy of the request's SamplingParams.  0: the log-probability and rank of every
+        generated token; 1..20: the top N (id, log-probability) pairs as well.  The values are the model's distribution at the
+        request's temperature, top_k / top_p not applied (include/jacobiforcing.h: jf_logprobs_rows).  Autoregressive outputs
+        gain "logprobs" / "ranks" [/ "top_logprobs"], rollout records "answer_logprobs" [/ "answer_top_logprobs"]."""
+        if logprobs is not None:
+            lp_list = list(logprobs) if isinstance(logprobs, (list, tuple)) else [logprobs] * len(prompts)
+            if len(lp_list) != len(prompts):
+                raise ValueError(f"logprobs: {len(lp_list)} values for {len(prompts)} prompts")
+            for n in lp_list:
+                if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 20):
+                    raise ValueError(f"logprobs must be None or an int in 0..20, got {n!r}")
+            if not isinstance(sampling_params, list):
+                sampling_params = [sampling_params] * len(prompts)
+            if len(sampling_params) != len(prompts):
+                raise ValueError(f"logprobs: {len(sampling_params)} sampling parameters for {len(prompts)} prompts")
+            sampling_params = [copy.copy(sp) for sp in sampling_params]
+            for sp, n in zip(sampling_params, lp_list):
+                if n is not None:
+                    sp.logprobs = int(n)
         pbar = None
         if use_tqdm:
             from tqdm.auto import tqdm
@@ -128,4 +158,5 @@ class LLMEngine:
             toks = [int(t) for t in outputs[seq_id]]
             text = self.tokenizer.decode(toks) if self.tokenizer is not None else ""
             res.append({"text": text, "token_ids": toks})
+            res[-1].update(self._logprob_outputs.pop(seq_id, {}))   # "logprobs", "ranks" [, "top_logprobs"]: only for requests that asked
         return res

@@ -212,6 +212,7 @@ class ModelRunner:
         self.jacobi_decoder = None
         self._mb_decoders = {}
         self._ar_sampler = None                                   # ops.ARSampler, built at the first seeded autoregressive draw
+        self._logprob_rows = None                                 # ops.LogprobRows, built when the first request asks for log-probabilities
         self.profiler = ProfileTimer(self.device)
         self._kv_host = [0] * self.max_rows
         self._logit_idx = {}
@@ -480,6 +481,12 @@ class ModelRunner:
         for seq in seqs:
             seq.num_cached_tokens = len(seq)
         temps = [float(seq.temperature) for seq in seqs]
+        toks = self._ar_tokens(seqs, temps, logits)
+        if any(getattr(getattr(seq, "sampling_params", None), "logprobs", None) is not None for seq in seqs):
+            self._ar_logprobs(seqs, temps, logits, toks)
+        return toks
+
+    def _ar_tokens(self, seqs: List[Sequence], temps: List[float], logits: torch.Tensor) -> list:
         if all(t == 0.0 for t in temps):
             return [int(t) for t in ops.argmax_rows(logits).cpu().tolist()]
         toks = self._ar_sample_seeded(seqs, temps, logits)      # the rows of the batched HIP sampler (None: a row of the loop below)
@@ -505,6 +512,49 @@ class ModelRunner:
                     p = torch.zeros_like(p).scatter_(-1, si, sp / sp.sum(dim=-1, keepdim=True).clamp_min(1e-12))
                 toks[i] = int(torch.argmax(p / torch.empty_like(p).exponential_(1).clamp_min_(1e-10), dim=-1)[0])
         return toks
+
+    def _ar_logprobs(self, seqs: List[Sequence], temps: List[float], logits: torch.Tensor, toks: list) -> None:
+        """Log-probability, rank and top N of this step's token of every request that planted ``logprobs`` on its SamplingParams
+        (read with getattr like seed / top_k / top_p: None or absent is off, 0 the chosen token's values, 1..20 the top N as
+        well): ``ops.LogprobRows`` on the asking rows, grouped by the temperature they were decoded at (greedy rows: 1.0).  It is
+        the model's distribution at that temperature — top_k / top_p are not applied.  The values are stored on the request at
+        index j = seq.num_completion_tokens at the draw (assigned, not appended: a pre-empted request is prefilled again and
+        draws token j again)."""
+        ask = {}
+        for i, seq in enumerate(seqs):
+            n = getattr(getattr(seq, "sampling_params", None), "logprobs", None)
+            if n is not None:
+                n = int(n)
+                if not 0 <= n <= 20:
+                    raise ValueError(f"logprobs must lie in 0..20, got {n}")
+                ask[i] = n
+        if self._logprob_rows is None:
+            self._logprob_rows = ops.LogprobRows(self.device, self.max_rows)
+        lp = self._logprob_rows
+        groups: dict = {}
+        for i in ask:
+            groups.setdefault(temps[i] if temps[i] > 0.0 else 1.0, []).append(i)
+        order, at = [], 0
+        for t, rows in groups.items():
+            if len(rows) == len(seqs):
+                sub = logits
+            else:
+                sub = logits.index_select(0, torch.tensor(rows, dtype=torch.int64).to(logits.device, non_blocking=True))
+            lp.run(sub, [toks[i] for i in rows], t, max(ask[i] for i in rows), at=at)
+            order += rows
+            at += len(rows)
+        lps, ranks, ids, tlp = lp.fetch(at)
+        for k, i in enumerate(order):
+            seq, n = seqs[i], ask[i]
+            j = seq.num_completion_tokens
+            for name, val in (("_logprobs", float(lps[k])), ("_ranks", int(ranks[k])),
+                              ("_top_logprobs", [(int(a), float(b)) for a, b in zip(ids[k, :n], tlp[k, :n])])):
+                lst = getattr(seq, name, None)
+                if lst is None:
+                    lst = []
+                    setattr(seq, name, lst)
+                lst.extend([None] * (j + 1 - len(lst)))
+                lst[j] = val
 
     def _ar_sample_seeded(self, seqs: List[Sequence], temps: List[float], logits: torch.Tensor) -> list:
         """Tokens of the rows that ``ops.ARSampler`` samples, None for every other row.  A request with ``temperature > 0`` goes
@@ -548,6 +598,11 @@ class ModelRunner:
         if mb and len(mb) != len(seqs) or jac and len(jac) != len(seqs):
             raise NotImplementedError("Mixed decode strategies in same batch not supported. "
                                       f"Got {len(jac)} Jacobi, {len(mb)} multiblock and {len(seqs) - len(jac) - len(mb)} autoregressive sequences.")
+        if (mb or jac) and any(getattr(getattr(s, "sampling_params", None), "logprobs", None) is not None
+                               and not getattr(s, "jacobi_on_policy", False) for s in seqs):
+            raise NotImplementedError("logprobs: the engine's jacobi chunk loop and the multiblock decoder keep their committed "
+                                      "tokens in device rings; log-probabilities there are a follow-up (a ring of floats beside "
+                                      "the token rings). Use decode_strategy='autoregressive' or on-policy rollouts.")
         if mb:
             if is_prefill:
                 for s in seqs:

@@ -19,16 +19,17 @@ class LLM(LLMEngine):
                  jacobi_enabled: Optional[bool] = None, jacobi_block_len: Optional[int] = None,
                  jacobi_num_blocks: Optional[int] = None, jacobi_spawn_ratio: Optional[float] = None,
                  jacobi_lookahead_start_ratio: Optional[float] = None, jacobi_ngram_pool_size: Optional[int] = None,
-                 seed=None, **kwargs: Any):
+                 seed=None, logprobs=None, **kwargs: Any):
         """``seed`` (not in the reference): an int gives request i the seed ``seed + i``, a list one value per prompt (None: nothing
         is planted on that request).  A seeded autoregressive request with temperature > 0 is sampled by ``ops.ARSampler`` from its own
-        counter-based stream (``ops.ar_stream``): its tokens do not depend on the batch or on torch's global generator."""
+        counter-based stream (``ops.ar_stream``): its tokens do not depend on the batch or on torch's global generator.
+        ``logprobs`` (not in the reference): see ``LLMEngine.generate``."""
         if sampling_params is None:
             sampling_params = SamplingParams()
 
         def replace_planted(sp: SamplingParams, **upd) -> SamplingParams:
             # dataclasses.replace builds a new object from the FIELDS: what a caller planted beside them (top_k, top_p,
-            # jacobi_lockstep, seed: no such fields upstream) is carried across by hand
+            # jacobi_lockstep, seed, logprobs: no such fields upstream) is carried across by hand
             new = replace(sp, **upd)
             names = {f.name for f in fields(sp)}
             for k, v in vars(sp).items():
@@ -77,4 +78,6 @@ class LLM(LLMEngine):
             for sp, sd in zip(sps, seeds):
                 if sd is not None:
                     sp.seed = int(sd)
+        if logprobs is not None:                                # LLMEngine.generate plants it, after the fold and the seeds
+            kwargs["logprobs"] = logprobs
         return super().generate(prompts, sps, **kwargs)

@@ -1265,9 +1265,12 @@ class OnPolicyStepper(_OnPolicyCore):
         self.cursors = torch.zeros((2,), dtype=torch.int64, device=dev)             # uniforms, multinomial
 
     def step(self, proposed: torch.Tensor, logits: torch.Tensor, temperature: float, cursors: Sequence[int], top_k: int = 0,
-             top_p: float = 0.0):
+             top_p: float = 0.0, logprobs: Optional["LogprobRows"] = None, top_n: int = 0):
         """proposed [R] int64, logits [R, V] -> (row dict, committed list, redraft list [R] (valid from n_committed)).
-        ``top_k`` / ``top_p`` (``active_filters``): the rows go through jf_rs_filter first (JDO:99-136, the same filters)."""
+        ``top_k`` / ``top_p`` (``active_filters``): the rows go through jf_rs_filter first (JDO:99-136, the same filters).
+        ``logprobs`` (a ``LogprobRows``): jf_logprobs_rows is queued behind the step on the same rows with the step's device
+        ``committed`` array as the chosen ids; its outputs ride this call's read-back and synchronise, and a fourth value is
+        returned: (logprobs [R], top_ids [R, top_n], top_logprobs [R, top_n]) as numpy — rows from n_committed on are stale."""
         R = int(proposed.numel())
         if logits.dim() != 2 or logits.shape[0] != R:
             raise ValueError(f"forward must return logits [1, {R}, vocab], got {tuple(logits.shape)}")     # JDO:392-393
@@ -1288,12 +1291,17 @@ class OnPolicyStepper(_OnPolicyCore):
                                         _ptr(self.m_stream), self.m_stream.numel(), c_ptr(1),
                                         _ptr(cm), _ptr(rd), _ptr(self.row_dev), _ptr(self.step_ws),
                                         self.step_ws.numel() * 8, _ptr(filt), _stream(dev)), "jf_rs_onpolicy_step")
+        if logprobs is not None:
+            logprobs.run(flat, cm[:R], temperature, top_n)
         self.row_host.copy_(self.row_dev, non_blocking=True)
         self.out_host[:, :R].copy_(self.out[:, :R], non_blocking=True)
         if dev.type == "cuda":
             torch.cuda.current_stream(dev).synchronize()
         row = self._record(self.row_host.tolist())
         n = row["n_committed"]
+        if logprobs is not None:
+            lps, _, ids, tlp = logprobs.fetch(R, synchronize=False)
+            return row, self.out_host[0, :n].tolist(), self.out_host[1, :R].tolist(), (lps, ids, tlp)
         return row, self.out_host[0, :n].tolist(), self.out_host[1, :R].tolist()
 
 
@@ -1326,10 +1334,13 @@ class OnPolicyBatchStepper(_OnPolicyCore):
         self.cursors = torch.zeros((self.max_rows, 2), dtype=torch.int64, device=dev)
 
     def step(self, proposed: torch.Tensor, n_rows: Sequence[int], logits: torch.Tensor, temperature: float,
-             seq_index: Sequence[int], top_k: int = 0, top_p: float = 0.0):
+             seq_index: Sequence[int], top_k: int = 0, top_p: float = 0.0, logprobs: Optional["LogprobRows"] = None,
+             top_n: int = 0):
         """proposed [G, Lm] int64 (row g: its n_rows[g] proposals, then padding), logits [G, Lm, V], seq_index [G]: which
         sequence (stream, cursors) each row belongs to -> (row dicts, committed lists, redraft lists [n_rows[g]], valid from
-        n_committed), one of each per row."""
+        n_committed), one of each per row.  ``logprobs`` (a ``LogprobRows``): as in ``OnPolicyStepper.step`` — flat row
+        g * Lm + t of the logits is chosen id committed[g][t]; the fourth value is a list of G triples (logprobs [n_rows[g]],
+        top_ids [n_rows[g], top_n], top_logprobs [n_rows[g], top_n])."""
         G, Lm = int(proposed.shape[0]), int(proposed.shape[1])
         if logits.dim() != 3 or logits.shape[0] != G or logits.shape[1] != Lm:
             raise ValueError(f"forward must return logits [{G}, {Lm}, vocab], got {tuple(logits.shape)}")          # JDO:392-393
@@ -1358,6 +1369,8 @@ class OnPolicyBatchStepper(_OnPolicyCore):
                                               _ptr(filt), _stream(dev)), "jf_rs_onpolicy_step_batch")
         if not whole:
             self.cursors.index_copy_(0, idx, cur)
+        if logprobs is not None:
+            logprobs.run(flat, cm, temperature, top_n)
         end = 2 * n + G * (N.OP_ROW_INTS // 2)
         self.out_host[:end].copy_(self.out[:end], non_blocking=True)
         if dev.type == "cuda":
@@ -1372,6 +1385,10 @@ class OnPolicyBatchStepper(_OnPolicyCore):
             out_rows.append(row)
             out_cm.append(host[g * Lm:g * Lm + row["n_committed"]].tolist())
             out_rd.append(host[n + g * Lm:n + g * Lm + int(n_rows[g])].tolist())
+        if logprobs is not None:
+            lps, _, ids, tlp = logprobs.fetch(n, synchronize=False)
+            sl = [slice(g * Lm, g * Lm + int(n_rows[g])) for g in range(G)]
+            return out_rows, out_cm, out_rd, [(lps[s_], ids[s_], tlp[s_]) for s_ in sl]
         return out_rows, out_cm, out_rd
 
 
@@ -1504,3 +1521,99 @@ class ARSampler:
         for k, b in enumerate(order):
             toks[b] = int(got[k])
         return toks
+
+
+# --------------------------------------------------------------------------------------------
+# per-token log-probabilities (jf_logprobs_rows)
+# --------------------------------------------------------------------------------------------
+class LogprobRows:
+    """Log-probability and rank of one chosen id per row and the row's top N (include/jacobiforcing.h: jf_logprobs_rows — the
+    model's distribution at the request's temperature, top_k / top_p not applied).  ``run`` queues the two launches on the
+    current stream and starts the non-blocking read-back into pinned mirrors; ``fetch`` returns numpy arrays once the stream
+    is synchronised.  The halves are separate so that a caller with a read-back of its own (the rollout steppers) shares
+    that one synchronise: it calls ``fetch(rows, synchronize=False)`` behind it.  Several ``run`` calls may precede one
+    ``fetch`` (``at``: the first output row of the call — the groups of a decode step that differ in temperature)."""
+
+    def __init__(self, device, max_rows: int = 64):
+        self.device = torch.device(device)
+        self.ws = torch.zeros((2,), dtype=torch.float64, device=self.device)      # grown to jf_logprobs_workspace_bytes on demand
+        self._ws_need: dict = {}
+        self._calls: list = []                                                    # (first row, rows, top_n) of the runs since the last fetch
+        self._alloc(int(max_rows))
+
+    def _alloc(self, n: int) -> None:
+        dev, pin, T = self.device, self.device.type == "cuda", N.LOGPROBS_MAX_TOP
+        self.rows = n
+        self.logprob = torch.zeros((n,), dtype=torch.float32, device=dev)
+        self.rank = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.top_ids = torch.zeros((n * T,), dtype=torch.int64, device=dev)       # a call's [R, top_n] block starts at row * T
+        self.top_lp = torch.zeros((n * T,), dtype=torch.float32, device=dev)
+        self.chosen = torch.zeros((n,), dtype=torch.int64, device=dev)
+        self.logprob_host = torch.zeros((n,), dtype=torch.float32, pin_memory=pin)
+        self.rank_host = torch.zeros((n,), dtype=torch.int32, pin_memory=pin)
+        self.top_ids_host = torch.zeros((n * T,), dtype=torch.int64, pin_memory=pin)
+        self.top_lp_host = torch.zeros((n * T,), dtype=torch.float32, pin_memory=pin)
+        self.chosen_host = torch.zeros((n,), dtype=torch.int64, pin_memory=pin)
+
+    def run(self, logits: torch.Tensor, chosen, temperature: float, top_n: int = 0, at: int = 0) -> None:
+        """logits [R, V] on the device (unit inner stride, else copied); chosen: R ids as a device int64 tensor or a host
+        list; top_n in 0..20.  Outputs go to rows at .. at + R - 1."""
+        if logits.dim() != 2:
+            raise ValueError(f"logits must be [R, V], got {tuple(logits.shape)}")
+        R, V = logits.shape
+        top_n, at = int(top_n), int(at)
+        if not 0 <= top_n <= N.LOGPROBS_MAX_TOP:
+            raise ValueError(f"top_n must lie in 0..{N.LOGPROBS_MAX_TOP}, got {top_n}")
+        if R == 0:
+            return
+        if at + R > self.rows:
+            if self._calls:
+                raise RuntimeError("LogprobRows: capacity exceeded between run() and fetch()")
+            self._alloc(max(at + R, 2 * self.rows))
+        dev, lib, T = self.device, N.lib(), N.LOGPROBS_MAX_TOP
+        flat = logits if logits.stride(1) == 1 else logits.contiguous()
+        stride = flat.stride(0) if R > 1 else V
+        if isinstance(chosen, torch.Tensor):
+            ch = chosen.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+            if ch.numel() != R:
+                raise ValueError(f"chosen holds {ch.numel()} ids for {R} rows")
+        else:
+            if len(chosen) != R:
+                raise ValueError(f"chosen holds {len(chosen)} ids for {R} rows")
+            self.chosen_host[at:at + R].copy_(torch.tensor([int(c) for c in chosen], dtype=torch.int64))
+            ch = self.chosen[at:at + R]
+            ch.copy_(self.chosen_host[at:at + R], non_blocking=True)
+        need = self._ws_need.get((R, V, top_n))
+        if need is None:
+            need = self._ws_need[(R, V, top_n)] = int(lib.jf_logprobs_workspace_bytes(R, V, top_n))
+        self.ws = _grown(self.ws, need + 16)
+        ids, tlp = self.top_ids[at * T:at * T + R * top_n], self.top_lp[at * T:at * T + R * top_n]
+        N.check(lib.jf_logprobs_rows(_ptr(flat), _dtype_code(flat), R, V, stride, float(temperature), _ptr(ch), top_n,
+                                     _ptr(self.logprob[at:at + R]), _ptr(self.rank[at:at + R]), _ptr(ids) if top_n else None,
+                                     _ptr(tlp) if top_n else None, _ptr(self.ws), self.ws.numel() * 8, _stream(dev)),
+                "jf_logprobs_rows")
+        self.logprob_host[at:at + R].copy_(self.logprob[at:at + R], non_blocking=True)
+        self.rank_host[at:at + R].copy_(self.rank[at:at + R], non_blocking=True)
+        if top_n:
+            self.top_ids_host[at * T:at * T + R * top_n].copy_(ids, non_blocking=True)
+            self.top_lp_host[at * T:at * T + R * top_n].copy_(tlp, non_blocking=True)
+        self._calls.append((at, R, top_n))
+
+    def fetch(self, rows: Optional[int] = None, synchronize: bool = True):
+        """(logprobs float32 [rows], ranks int32 [rows], top_ids int64 [rows, N], top_logprobs float32 [rows, N]) of the runs
+        since the last fetch, N the largest top_n among them (a run with a smaller one: id -1 / -inf in the other slots)."""
+        calls, self._calls = self._calls, []
+        if rows is None:
+            rows = max((a + r for a, r, _ in calls), default=0)
+        if synchronize and self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        T = N.LOGPROBS_MAX_TOP
+        nmax = max((n for _, _, n in calls), default=0)
+        ids = np.full((rows, nmax), -1, dtype=np.int64)
+        tlp = np.full((rows, nmax), -np.inf, dtype=np.float32)
+        ih, th = self.top_ids_host.numpy(), self.top_lp_host.numpy()
+        for a, r, n in calls:
+            if n:
+                ids[a:a + r, :n] = ih[a * T:a * T + r * n].reshape(r, n)
+                tlp[a:a + r, :n] = th[a * T:a * T + r * n].reshape(r, n)
+        return self.logprob_host[:rows].numpy().copy(), self.rank_host[:rows].numpy().copy(), ids, tlp
