@@ -336,6 +336,24 @@ JF_API int jf_rope_kv_append(const void *qkv, int dtype, int64_t N, int32_t T, i
                       void *k_cache, void *v_cache, const int64_t *slot_main, int64_t S_max,
                       void *k_cand, void *v_cand, const int64_t *slot_cand, int64_t T_max, void *stream);
 
+/* The same launch with the per-head RMSNorm of q and k in front of the rotation (Qwen3's q_norm / k_norm; the reference applies
+ * them in inference_engine/models/qwen3.py:67-84 when the checkpoint has no QKV bias).  For every q head and every k head
+ * x[0..D) of every token, with w = q_norm_w for q heads and k_norm_w for k heads ([D] each, in the dtype of qkv):
+ *   y[i] = x[i] * rsqrt(mean_j x[j]^2 + eps) * w[i]          in float32
+ * then the rotate-half RoPE of jf_rope_kv_append on y in float32, and ONE rounding at the store.  No intermediate is rounded
+ * to bf16: HF rounds the normalised head to bf16, rounds again after the multiplication by w and rotates in bf16, so bf16
+ * results differ from HF's in the last bits exactly as the fused RoPE's do; fp32 results differ by summation order only.
+ * v heads are copied bit for bit.  An all-zero head gives zeros (rsqrt(eps) is finite for eps > 0).
+ * Layout, slots, candidate scratch and the meaning of -1 are jf_rope_kv_append's.  JF_E_INVALID on a null pointer (the norm
+ * weights included), eps negative or NaN, or a bad shape; N <= 0 returns JF_OK.  dtype JF_F32 or JF_BF16.
+ * 16-byte accesses are used when every row start and both weight rows are 16-byte aligned and (D/2) / (16 / element size) is
+ * a power of two (D = 128, 64, 32); every other even D and any alignment runs one wavefront per (token, head). */
+JF_API int jf_qknorm_rope_kv_append(const void *qkv, int dtype, int64_t N, int32_t T, int32_t nq, int32_t nkv, int32_t D,
+                      const void *q_norm_w, const void *k_norm_w, float eps,
+                      const int32_t *positions, const float *cos_table, const float *sin_table, void *q_out,
+                      void *k_cache, void *v_cache, const int64_t *slot_main, int64_t S_max,
+                      void *k_cand, void *v_cand, const int64_t *slot_cand, int64_t T_max, void *stream);
+
 /* SwiGLU gate of the MLP in one pass: out[m, i] = silu(gu[m, i]) * gu[m, I + i] for the fused gate/up projection output
  * gu [M, 2*I] (row-major), out [M, I].  fp32 arithmetic, one rounding; dtype JF_F32 or JF_BF16. */
 JF_API int jf_swiglu(const void *gu, int dtype, int64_t M, int64_t I, void *out, void *stream);

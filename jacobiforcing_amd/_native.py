@@ -150,6 +150,8 @@ _SIGNATURES = {
     "jf_kv_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "jf_rope_kv_append": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                     _vp, _i64, _vp]),
+    "jf_qknorm_rope_kv_append": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "jf_swiglu": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp]),
     "jf_attn_out_relayout": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp]),
     "jf_forward_plan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, C.c_int, _vp, _vp, _vp, _vp]),

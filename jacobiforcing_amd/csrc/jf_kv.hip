@@ -227,6 +227,194 @@ extern "C" int jf_rope_kv_append(const void *qkv, int dtype, int64_t N, int32_t 
     return check_launch("rope_kv_append_kernel");
 }
 
+// ---- per-head RMSNorm of q and k (Qwen3's q_norm / k_norm) in front of the same RoPE + Q re-layout + KV append ------------
+// y = x * rsqrt(mean x^2 + eps) * w and the rotation of y stay in fp32; the store rounds once.  Layout contract and slots are
+// jf_rope_kv_append's.  No LDS, no atomics, nothing waits: a head's sum of squares lives in the registers of the lanes that
+// own the head and is reduced with cross-lane shuffles.
+template <typename T, typename F>
+__device__ __forceinline__ void qkn_for_each_dst(int h, int64_t tok, int Tlen, int nq, int nkv, int D, T *q_out, T *k_cache, T *v_cache,
+                                                 const int64_t *slot_main, int64_t S_max, T *k_cand, T *v_cand,
+                                                 const int64_t *slot_cand, int64_t T_max, F put) {
+    if (h < nq) {
+        const int G = nq / nkv;
+        const int kvh = h / G, g = h - kvh * G;
+        const int64_t r = tok / Tlen, t = tok - r * Tlen;
+        put(q_out + (((r * nkv + kvh) * (int64_t)G * Tlen) + (int64_t)g * Tlen + t) * D);
+        return;
+    }
+    const bool is_v = h >= nq + nkv;
+    const int kvh = is_v ? h - nq - nkv : h - nq;
+    const int64_t sm = slot_main[tok];
+    if (sm >= 0) {
+        const int64_t brow = sm / S_max, pos = sm - brow * S_max;
+        put((is_v ? v_cache : k_cache) + ((brow * nkv + kvh) * S_max + pos) * D);
+    }
+    if (slot_cand) {
+        const int64_t sc = slot_cand[tok];
+        if (sc >= 0) {
+            const int64_t brow = sc / T_max, pos = sc - brow * T_max;
+            put((is_v ? v_cand : k_cand) + ((brow * nkv + kvh) * T_max + pos) * D);
+        }
+    }
+}
+
+// General path: one wavefront per (token, head), a strided loop over the head and a full-wave reduction.  Any even D, any
+// alignment.  v heads are copied as bits.
+template <typename T>
+__global__ __launch_bounds__(256) void qknorm_rope_kv_append_kernel(const T *__restrict__ qkv, int64_t N, int Tlen, int nq, int nkv, int D,
+                                                                     const T *__restrict__ qn, const T *__restrict__ kn, float eps,
+                                                                     const int32_t *__restrict__ positions,
+                                                                     const float *__restrict__ cos_t, const float *__restrict__ sin_t,
+                                                                     T *__restrict__ q_out, T *__restrict__ k_cache,
+                                                                     T *__restrict__ v_cache, const int64_t *__restrict__ slot_main,
+                                                                     int64_t S_max, T *__restrict__ k_cand, T *__restrict__ v_cand,
+                                                                     const int64_t *__restrict__ slot_cand, int64_t T_max) {
+    const int half = D >> 1;
+    const int heads = nq + 2 * nkv;
+    const int lane = threadIdx.x & 63;
+    const int64_t th = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (th >= N * heads) return;                              // th is the same for the 64 lanes: a wavefront leaves as a whole
+    const int h = (int)(th % heads);
+    const int64_t tok = th / heads;
+    const T *src = qkv + (tok * heads + h) * D;
+    const bool rot = h < nq + nkv;                            // wavefront-uniform
+    float inv = 0.f;
+    if (rot) {
+        float ss = 0.f;
+        for (int i = lane; i < D; i += 64) { const float x = ld_f(src + i); ss += x * x; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+        inv = rsqrtf(ss / (float)D + eps);
+    }
+    const T *w = h < nq ? qn : kn;
+    const int64_t pos = rot ? positions[tok] : 0;
+    for (int i = lane; i < half; i += 64) {
+        T o1 = src[i], o2 = src[half + i];
+        if (rot) {
+            const float y1 = ld_f(&o1) * inv * ld_f(w + i), y2 = ld_f(&o2) * inv * ld_f(w + half + i);
+            const float c = cos_t[pos * half + i], sn = sin_t[pos * half + i];
+            st_f(&o1, y1 * c - y2 * sn);
+            st_f(&o2, y2 * c + y1 * sn);
+        }
+        qkn_for_each_dst(h, tok, Tlen, nq, nkv, D, q_out, k_cache, v_cache, slot_main, S_max, k_cand, v_cand, slot_cand, T_max,
+                         [&](T *dst) { dst[i] = o1; dst[half + i] = o2; });
+    }
+}
+
+// 16-byte path, the lane mapping of rope_kv_append_vec_kernel: a lane owns EPV pairs (x1[i], x2[i]) of one (token, head), the
+// lph = (D/2)/EPV lanes of a head are consecutive.  lph is a power of two <= 64 (checked by the host), so a head's lanes are
+// an lph-aligned group inside one wavefront (256 and 64 are multiples of lph) and __shfl_xor over offsets < lph stays inside
+// the group.  The grid covers N*heads*lph lanes, a whole number of groups: the early return below takes whole groups, never
+// part of one, so every lane a shuffle reads from is active.
+template <typename T, int EPV>
+__global__ __launch_bounds__(256) void qknorm_rope_kv_append_vec_kernel(const T *__restrict__ qkv, int64_t N, int Tlen, int nq, int nkv,
+                                                                         int D, const T *__restrict__ qn, const T *__restrict__ kn,
+                                                                         float eps, const int32_t *__restrict__ positions,
+                                                                         const float *__restrict__ cos_t, const float *__restrict__ sin_t,
+                                                                         T *__restrict__ q_out, T *__restrict__ k_cache,
+                                                                         T *__restrict__ v_cache, const int64_t *__restrict__ slot_main,
+                                                                         int64_t S_max, T *__restrict__ k_cand, T *__restrict__ v_cand,
+                                                                         const int64_t *__restrict__ slot_cand, int64_t T_max) {
+    const int half = D >> 1;
+    const int lph = half / EPV;                               // lanes per head
+    const int heads = nq + 2 * nkv;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= N * heads * lph) return;
+    const int i0 = (int)(gid % lph) * EPV;
+    const int64_t th = gid / lph;
+    const int h = (int)(th % heads);
+    const int64_t tok = th / heads;
+    const T *src = qkv + (tok * heads + h) * D;
+    alignas(16) T a[EPV], b[EPV], oa[EPV], ob[EPV];
+    *reinterpret_cast<uint4 *>(a) = *reinterpret_cast<const uint4 *>(src + i0);
+    *reinterpret_cast<uint4 *>(b) = *reinterpret_cast<const uint4 *>(src + half + i0);
+    float ss = 0.f;                                           // the lane's 2*EPV squares (v heads too: keeps the shuffles uniform)
+#pragma unroll
+    for (int j = 0; j < EPV; ++j) {
+        const float x1 = ld_f(a + j), x2 = ld_f(b + j);
+        ss += x1 * x1 + x2 * x2;
+    }
+    for (int o = lph >> 1; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    if (h < nq + nkv) {                                       // normalise and rotate q and k heads, v passes through
+        const float inv = rsqrtf(ss / (float)D + eps);
+        const T *w = h < nq ? qn : kn;
+        alignas(16) T wa[EPV], wb[EPV];
+        *reinterpret_cast<uint4 *>(wa) = *reinterpret_cast<const uint4 *>(w + i0);
+        *reinterpret_cast<uint4 *>(wb) = *reinterpret_cast<const uint4 *>(w + half + i0);
+        const int64_t pos = positions[tok];
+        alignas(16) float c[EPV], sn[EPV];
+#pragma unroll
+        for (int j = 0; j < EPV; j += 4) {
+            *reinterpret_cast<float4 *>(c + j) = *reinterpret_cast<const float4 *>(cos_t + pos * half + i0 + j);
+            *reinterpret_cast<float4 *>(sn + j) = *reinterpret_cast<const float4 *>(sin_t + pos * half + i0 + j);
+        }
+#pragma unroll
+        for (int j = 0; j < EPV; ++j) {
+            const float y1 = ld_f(a + j) * inv * ld_f(wa + j), y2 = ld_f(b + j) * inv * ld_f(wb + j);
+            st_f(oa + j, y1 * c[j] - y2 * sn[j]);
+            st_f(ob + j, y2 * c[j] + y1 * sn[j]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EPV; ++j) { oa[j] = a[j]; ob[j] = b[j]; }
+    }
+    qkn_for_each_dst(h, tok, Tlen, nq, nkv, D, q_out, k_cache, v_cache, slot_main, S_max, k_cand, v_cand, slot_cand, T_max, [&](T *dst) {
+        *reinterpret_cast<uint4 *>(dst + i0) = *reinterpret_cast<const uint4 *>(oa);
+        *reinterpret_cast<uint4 *>(dst + half + i0) = *reinterpret_cast<const uint4 *>(ob);
+    });
+}
+
+extern "C" int jf_qknorm_rope_kv_append(const void *qkv, int dtype, int64_t N, int32_t T, int32_t nq, int32_t nkv, int32_t D,
+                                        const void *q_norm_w, const void *k_norm_w, float eps, const int32_t *positions,
+                                        const float *cos_table, const float *sin_table, void *q_out, void *k_cache, void *v_cache,
+                                        const int64_t *slot_main, int64_t S_max, void *k_cand, void *v_cand, const int64_t *slot_cand,
+                                        int64_t T_max, void *stream) {
+    if (N <= 0) return JF_OK;
+    if (!qkv || !positions || !cos_table || !sin_table || !q_out || !k_cache || !v_cache || !slot_main)
+        return fail(JF_E_INVALID, "jf_qknorm_rope_kv_append: null pointer");
+    if (!q_norm_w || !k_norm_w) return fail(JF_E_INVALID, "jf_qknorm_rope_kv_append: null norm weight");
+    if (!(eps >= 0.f)) return fail(JF_E_INVALID, "jf_qknorm_rope_kv_append: eps %g (must be >= 0)", (double)eps);
+    if (dtype != JF_F32 && dtype != JF_BF16) return fail(JF_E_INVALID, "jf_qknorm_rope_kv_append: dtype %d", dtype);
+    if (T <= 0 || N % T != 0 || nq <= 0 || nkv <= 0 || nq % nkv != 0 || D <= 0 || (D & 1) || S_max <= 0)
+        return fail(JF_E_INVALID, "jf_qknorm_rope_kv_append: bad shape N=%lld T=%d nq=%d nkv=%d D=%d", (long long)N, T, nq, nkv, D);
+    if (slot_cand && (!k_cand || !v_cand || T_max <= 0)) return fail(JF_E_INVALID, "jf_qknorm_rope_kv_append: candidate cache missing");
+    hipStream_t s = (hipStream_t)stream;
+    const int esz = dtype == JF_F32 ? 4 : 2, epv = 16 / esz;
+    const int64_t rows = N * (nq + 2 * nkv);                  // (token, head) rows
+    auto al16 = [](const void *p) { return ((uintptr_t)p) % 16 == 0; };
+    static const bool force_scalar = [] { const char *e = getenv("JF_ROPE_SCALAR"); return e && *e == '1'; }();   // A/B in tools/
+    // 16-byte path: jf_rope_kv_append's conditions, aligned weight rows, and a power-of-two number of lanes per head within a wavefront
+    const int lph = (D / 2) / epv;
+    const bool vec = !force_scalar && (D / 2) % epv == 0 && (D / 2) % 4 == 0 && lph <= 64 && (lph & (lph - 1)) == 0 && al16(qkv) &&
+                     al16(q_out) && al16(k_cache) && al16(v_cache) && al16(cos_table) && al16(sin_table) && al16(q_norm_w) &&
+                     al16(k_norm_w) && (!slot_cand || (al16(k_cand) && al16(v_cand)));
+    const int64_t blocks = vec ? (rows * lph + 255) / 256 : (rows + 3) / 4;     // general path: four wavefronts per workgroup
+    if (blocks > 0x7FFFFFFFll) return fail(JF_E_CAPACITY, "jf_qknorm_rope_kv_append: grid too large");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (vec) {
+        if (dtype == JF_F32)
+            qknorm_rope_kv_append_vec_kernel<float, 4><<<grid, block, 0, s>>>(
+                (const float *)qkv, N, T, nq, nkv, D, (const float *)q_norm_w, (const float *)k_norm_w, eps, positions, cos_table, sin_table,
+                (float *)q_out, (float *)k_cache, (float *)v_cache, slot_main, S_max, (float *)k_cand, (float *)v_cand, slot_cand, T_max);
+        else
+            qknorm_rope_kv_append_vec_kernel<uint16_t, 8><<<grid, block, 0, s>>>(
+                (const uint16_t *)qkv, N, T, nq, nkv, D, (const uint16_t *)q_norm_w, (const uint16_t *)k_norm_w, eps, positions, cos_table,
+                sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache, slot_main, S_max, (uint16_t *)k_cand,
+                (uint16_t *)v_cand, slot_cand, T_max);
+        return check_launch("qknorm_rope_kv_append_vec_kernel");
+    }
+    if (dtype == JF_F32)
+        qknorm_rope_kv_append_kernel<float><<<grid, block, 0, s>>>(
+            (const float *)qkv, N, T, nq, nkv, D, (const float *)q_norm_w, (const float *)k_norm_w, eps, positions, cos_table, sin_table,
+            (float *)q_out, (float *)k_cache, (float *)v_cache, slot_main, S_max, (float *)k_cand, (float *)v_cand, slot_cand, T_max);
+    else
+        qknorm_rope_kv_append_kernel<uint16_t><<<grid, block, 0, s>>>(
+            (const uint16_t *)qkv, N, T, nq, nkv, D, (const uint16_t *)q_norm_w, (const uint16_t *)k_norm_w, eps, positions, cos_table,
+            sin_table, (uint16_t *)q_out, (uint16_t *)k_cache, (uint16_t *)v_cache, slot_main, S_max, (uint16_t *)k_cand,
+            (uint16_t *)v_cand, slot_cand, T_max);
+    return check_launch("qknorm_rope_kv_append_kernel");
+}
+
 // ---- SwiGLU gate: two 16-byte vectors of gate and of up per lane (four independent loads in flight), silu through the
 // hardware exp2 / rcp (x * rcp(1 + exp2(-x * log2 e)): ~6 VALU operations per element; the exact expf + IEEE division it
 // replaces cost ~35 and made the kernel VALU-bound at 2.6 TB/s, profiles/kernel_classes_r02.txt)

@@ -11,7 +11,9 @@ so the Jacobi loop body never has to copy the cache:
 
 It mirrors what the reference's forward computes (HF Qwen2: embed -> N x [RMSNorm, QKV+bias,
 RoPE, GQA attention, o_proj, RMSNorm, SwiGLU] -> RMSNorm -> lm_head, cf. MB:428-463 and
-inference_engine/models/qwen3.py:185-215) but shares no code with it.
+inference_engine/models/qwen3.py:185-215) but shares no code with it.  Dense Qwen3 checkpoints run
+through the same classes: no QKV bias, and a per-head RMSNorm of q and k in front of RoPE
+(``Qwen2Config.qk_norm``; inference_engine/models/qwen3.py:67-84).
 """
 from __future__ import annotations
 
@@ -30,6 +32,9 @@ from .. import ops
 # A/B switch (read once): 0 keeps the torch prelude and the torch attention-output copy on the GPU too.  Off the GPU the torch
 # code is the only path.
 FORWARD_GLUE = os.environ.get("JF_FORWARD_GLUE", "1") != "0"
+# A/B switch (read once) for qk_norm models (Qwen3): 0 normalises q and k in torch in front of the unchanged jf_rope_kv_append
+# launch on the GPU too.  Off the GPU the torch normalisation is the only path.
+QKNORM_FUSED = os.environ.get("JF_QKNORM_FUSED", "1") != "0"
 
 
 @dataclass
@@ -47,6 +52,8 @@ class Qwen2Config:
     tie_word_embeddings: bool = False
     eos_token_id: int = 151645
     pad_token_id: int = 151643
+    qk_norm: bool = False            # Qwen3: per-head RMSNorm of q and k in front of RoPE (self_attn.q_norm / k_norm)
+    attention_bias: bool = True      # Qwen2 / Qwen2.5: bias on the q/k/v projections
 
     @classmethod
     def qwen2_5_coder_7b(cls) -> "Qwen2Config":
@@ -59,14 +66,40 @@ class Qwen2Config:
                    num_attention_heads=heads, num_key_value_heads=kv_heads, head_dim=head_dim,
                    max_position_embeddings=4096, eos_token_id=vocab_size - 1, pad_token_id=vocab_size - 2)
 
+    @staticmethod
+    def _family(d: dict) -> dict:
+        """qk_norm / attention_bias of a HF config dict (Qwen2, Qwen2.5 or dense Qwen3), after refusing what this forward does not
+        compute: each refusal names the config field."""
+        mt = str(d.get("model_type") or "")
+        if "moe" in mt.lower():
+            raise ValueError(f"model_type {mt!r}: mixture-of-experts checkpoints are not supported")
+        if d.get("num_experts") is not None:
+            raise ValueError(f"num_experts = {d['num_experts']!r}: mixture-of-experts checkpoints are not supported")
+        other = sorted({str(t) for t in (d.get("layer_types") or []) if t != "full_attention"})
+        if other:
+            raise ValueError(f"layer_types contains {other}: only full_attention layers are supported")
+        if d.get("use_sliding_window"):
+            raise ValueError("use_sliding_window is true: sliding-window attention is not supported")
+        for key in ("rope_scaling", "rope_parameters"):
+            rp = d.get(key)
+            rt = rp.get("rope_type") if isinstance(rp, dict) else None
+            if rt not in (None, "default"):
+                raise ValueError(f"{key} has rope_type {rt!r}: only the default (unscaled) RoPE is supported")
+        return dict(qk_norm=mt == "qwen3", attention_bias=bool(d.get("attention_bias", mt != "qwen3")))
+
     @classmethod
     def from_json(cls, path) -> "Qwen2Config":
-        d = json.loads(Path(path).read_text())
+        return cls.from_dict(json.loads(Path(path).read_text()))
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "Qwen2Config":
+        """A HF ``config.json`` as a dict (Qwen2 / Qwen2.5 / dense Qwen3; no ``model_type``: Qwen2)."""
+        fam = cls._family(d)
         hd = d.get("head_dim") or d["hidden_size"] // d["num_attention_heads"]
         eos = d.get("eos_token_id", 151645)
         if isinstance(eos, list):
             eos = eos[0]
-        return cls(vocab_size=d["vocab_size"], hidden_size=d["hidden_size"], intermediate_size=d["intermediate_size"],
+        return cls(**fam, vocab_size=d["vocab_size"], hidden_size=d["hidden_size"], intermediate_size=d["intermediate_size"],
                    num_hidden_layers=d["num_hidden_layers"], num_attention_heads=d["num_attention_heads"],
                    num_key_value_heads=d.get("num_key_value_heads", d["num_attention_heads"]), head_dim=hd,
                    rms_norm_eps=d.get("rms_norm_eps", 1e-6),
@@ -90,36 +123,67 @@ class Qwen2Weights:
         self.embed = rnd(cfg.vocab_size, H)
         self.layers = []
         for _ in range(cfg.num_hidden_layers):
-            self.layers.append(dict(
+            # (the generator's draw order is part of the goldens: a config with a bias draws exactly what it always drew)
+            L = dict(
                 ln1=torch.ones(H, device=device, dtype=dtype),
-                wqkv=rnd((nq + 2 * nkv) * hd, H), bqkv=rnd((nq + 2 * nkv) * hd, std=0.01),
+                wqkv=rnd((nq + 2 * nkv) * hd, H), bqkv=rnd((nq + 2 * nkv) * hd, std=0.01) if cfg.attention_bias else None,
                 wo=rnd(H, nq * hd),
                 ln2=torch.ones(H, device=device, dtype=dtype),
-                wgu=rnd(2 * I, H), wd=rnd(H, I)))
+                wgu=rnd(2 * I, H), wd=rnd(H, I))
+            if cfg.qk_norm:
+                L["qn"] = torch.ones(hd, device=device, dtype=dtype)
+                L["kn"] = torch.ones(hd, device=device, dtype=dtype)
+            self.layers.append(L)
         self.norm = torch.ones(H, device=device, dtype=dtype)
         self.lm_head = self.embed if cfg.tie_word_embeddings else rnd(cfg.vocab_size, H)
 
-    def load_state_dict(self, sd, cfg: Qwen2Config) -> None:
-        """Adopt the tensors of a HF ``Qwen2ForCausalLM.state_dict()`` (fuses q/k/v and gate/up; casts to this dtype)."""
+    def _adopt(self, tensors, cfg: Qwen2Config, what: str) -> None:
+        """The one mapping from HF tensor names to this container (fuses q/k/v and gate/up; casts to this dtype and device).
+        Strict in both directions: a tensor the config calls for that ``tensors`` lacks, and a q_norm / k_norm / projection bias
+        the config does not call for, are errors that name the tensor — nothing is dropped silently."""
         dev, dt = self.embed.device, self.embed.dtype
-        get = lambda k: sd[k].detach().to(device=dev, dtype=dt)
+
+        def get(k):
+            if k not in tensors:
+                raise KeyError(f"{what}: tensor {k!r} is missing (the config calls for it: qk_norm={cfg.qk_norm}, "
+                               f"attention_bias={cfg.attention_bias})")
+            return tensors[k].detach().to(device=dev, dtype=dt)
+
+        def refuse(k, field):
+            if k in tensors:
+                raise ValueError(f"{what}: tensor {k!r} is present but the config has {field}: refusing to ignore it")
+
         self.embed = get("model.embed_tokens.weight")
         for i, L in enumerate(self.layers):
             pre = f"model.layers.{i}."
             L["ln1"] = get(pre + "input_layernorm.weight")
             L["ln2"] = get(pre + "post_attention_layernorm.weight")
             L["wqkv"] = torch.cat([get(pre + f"self_attn.{n}_proj.weight") for n in "qkv"], 0)
-            L["bqkv"] = torch.cat([get(pre + f"self_attn.{n}_proj.bias") for n in "qkv"], 0)
+            if cfg.attention_bias:
+                L["bqkv"] = torch.cat([get(pre + f"self_attn.{n}_proj.bias") for n in "qkv"], 0)
+            else:
+                L["bqkv"] = None
+                for n in "qkv":
+                    refuse(pre + f"self_attn.{n}_proj.bias", "attention_bias = false")
+            if cfg.qk_norm:
+                L["qn"] = get(pre + "self_attn.q_norm.weight")
+                L["kn"] = get(pre + "self_attn.k_norm.weight")
+            else:
+                for n in "qk":
+                    refuse(pre + f"self_attn.{n}_norm.weight", "no q/k norm (model_type is not qwen3)")
             L["wo"] = get(pre + "self_attn.o_proj.weight")
             L["wgu"] = torch.cat([get(pre + "mlp.gate_proj.weight"), get(pre + "mlp.up_proj.weight")], 0)
             L["wd"] = get(pre + "mlp.down_proj.weight")
         self.norm = get("model.norm.weight")
         self.lm_head = self.embed if cfg.tie_word_embeddings else get("lm_head.weight")
 
+    def load_state_dict(self, sd, cfg: Qwen2Config) -> None:
+        """Adopt the tensors of a HF ``Qwen2ForCausalLM`` / ``Qwen3ForCausalLM`` ``state_dict()``."""
+        self._adopt(sd, cfg, "state_dict")
+
     def load_safetensors(self, model_dir, cfg: Qwen2Config) -> None:
-        """Load a HF Qwen2 checkpoint directory (*.safetensors) when one is available."""
+        """Load a HF Qwen2 / Qwen3 checkpoint directory (*.safetensors) when one is available."""
         from safetensors import safe_open
-        nq, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         tensors = {}
         if not list(Path(model_dir).glob("*.safetensors")):
             raise FileNotFoundError(f"no *.safetensors under {model_dir}")
@@ -127,20 +191,7 @@ class Qwen2Weights:
             with safe_open(str(f), "pt", "cpu") as sf:
                 for k in sf.keys():
                     tensors[k] = sf.get_tensor(k)
-        dev, dt = self.embed.device, self.embed.dtype
-        get = lambda k: tensors[k].to(device=dev, dtype=dt)
-        self.embed = get("model.embed_tokens.weight")
-        for i, L in enumerate(self.layers):
-            pre = f"model.layers.{i}."
-            L["ln1"] = get(pre + "input_layernorm.weight")
-            L["ln2"] = get(pre + "post_attention_layernorm.weight")
-            L["wqkv"] = torch.cat([get(pre + f"self_attn.{n}_proj.weight") for n in "qkv"], 0)
-            L["bqkv"] = torch.cat([get(pre + f"self_attn.{n}_proj.bias") for n in "qkv"], 0)
-            L["wo"] = get(pre + "self_attn.o_proj.weight")
-            L["wgu"] = torch.cat([get(pre + "mlp.gate_proj.weight"), get(pre + "mlp.up_proj.weight")], 0)
-            L["wd"] = get(pre + "mlp.down_proj.weight")
-        self.norm = get("model.norm.weight")
-        self.lm_head = self.embed if cfg.tie_word_embeddings else get("lm_head.weight")
+        self._adopt(tensors, cfg, str(model_dir))
 
 
 def load_model_directory(model_dir, device, dtype=None, allow_random_init: bool = False):
@@ -221,9 +272,10 @@ class StaticKVCache:
 class Qwen2Model:
     @classmethod
     def from_hf(cls, hf_model, device=None, dtype=None) -> "Qwen2Model":
-        """Build the forward from a loaded ``transformers`` Qwen2ForCausalLM (route 2)."""
+        """Build the forward from a loaded ``transformers`` Qwen2ForCausalLM or Qwen3ForCausalLM (route 2)."""
         c = hf_model.config
-        cfg = Qwen2Config(vocab_size=c.vocab_size, hidden_size=c.hidden_size, intermediate_size=c.intermediate_size,
+        fam = Qwen2Config._family(c.to_dict() if hasattr(c, "to_dict") else dict(vars(c)))
+        cfg = Qwen2Config(**fam, vocab_size=c.vocab_size, hidden_size=c.hidden_size, intermediate_size=c.intermediate_size,
                           num_hidden_layers=c.num_hidden_layers, num_attention_heads=c.num_attention_heads,
                           num_key_value_heads=c.num_key_value_heads,
                           head_dim=getattr(c, "head_dim", None) or c.hidden_size // c.num_attention_heads,
@@ -265,6 +317,16 @@ class Qwen2Model:
         h = x.shape[-1] // 2
         x1, x2 = x[..., :h], x[..., h:]
         return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
+
+    def _qk_norm_(self, qkv: torch.Tensor, qn: torch.Tensor, kn: torch.Tensor) -> None:
+        """HF's Qwen3RMSNorm over head_dim on the q and k heads of the fused projection output [N, (nq+2nkv)*hd], in place."""
+        cfg = self.cfg
+        nq, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        heads = qkv.view(qkv.shape[0], nq + 2 * nkv, hd)
+        for sl, w in ((slice(0, nq), qn), (slice(nq, nq + nkv), kn)):
+            x = heads[:, sl]
+            xf = x.float()
+            x.copy_((xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + cfg.rms_norm_eps)).to(x.dtype) * w)
 
     def _mlp_residual(self, L, x2d, h2d):
         """x += down(silu(gate(h)) * up(h)) with the gate in one HIP launch and the residual in the GEMM epilogue (in place:
@@ -380,13 +442,22 @@ class Qwen2Model:
         elif not direct:
             rp = row_prompt.long()
 
+        # Qwen3's per-head RMSNorm of q and k: on the GPU inside the RoPE + KV-append launch (jf_qknorm_rope_kv_append), elsewhere (and
+        # with QKNORM_FUSED off: the kernel's A/B partner) in torch in front of the unchanged launch.  A model without the norms
+        # never looks the new entry point up.
+        qkn_fused = cfg.qk_norm and QKNORM_FUSED and dev.type == "cuda"
         x = w.embed[input_ids].view(R * T, cfg.hidden_size)                           # [R*T, H]
         for li, L in enumerate(w.layers):
             qkv = F.linear(self._norm(x, L["ln1"]), L["wqkv"], L["bqkv"])                 # [R*T, (nq+2nkv)*hd]
             # one HIP launch: RoPE on q/k, queries re-laid out per KV head, K/V rows appended to the cache(s) (a18)
-            qh = ops.rope_kv_append(qkv, T, nq, nkv, hd, pos32, self.cos, self.sin, cache.k[li], cache.v[li], slot_main,
-                                    cache.ck[li] if any_candidates else None, cache.cv[li] if any_candidates else None,
-                                    slot_cand if any_candidates else None)
+            kv_dst = (cache.k[li], cache.v[li], slot_main, cache.ck[li] if any_candidates else None,
+                      cache.cv[li] if any_candidates else None, slot_cand if any_candidates else None)
+            if qkn_fused:                                                              # Qwen3 on the GPU: q_norm / k_norm inside that launch
+                qh = ops.qknorm_rope_kv_append(qkv, T, nq, nkv, hd, L["qn"], L["kn"], cfg.rms_norm_eps, pos32, self.cos, self.sin, *kv_dst)
+            else:
+                if cfg.qk_norm:
+                    self._qk_norm_(qkv, L["qn"], L["kn"])
+                qh = ops.rope_kv_append(qkv, T, nq, nkv, hd, pos32, self.cos, self.sin, *kv_dst)
             if split:
                 if direct_a:
                     Ka, Va = cache.k[li][:, :, :S_cur], cache.v[li][:, :, :S_cur]

@@ -613,6 +613,33 @@ def rope_kv_append(qkv: torch.Tensor, T: int, nq: int, nkv: int, D: int, positio
     return q
 
 
+def qknorm_rope_kv_append(qkv: torch.Tensor, T: int, nq: int, nkv: int, D: int, qn: torch.Tensor, kn: torch.Tensor, eps: float,
+                          positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+                          v_cache: torch.Tensor, slot_main: torch.Tensor, k_cand: Optional[torch.Tensor] = None,
+                          v_cand: Optional[torch.Tensor] = None, slot_cand: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rope_kv_append with the per-head RMSNorm of q and k (weights qn / kn [D] in qkv's dtype, Qwen3) in front of the rotation:
+    fp32 throughout, one rounding at the store.  qkv [N, (nq+2nkv)*D] contiguous; returns q [R, nkv, G*T, D]."""
+    Ntok = qkv.shape[0]
+    if not qkv.is_contiguous() or qkv.shape[1] != (nq + 2 * nkv) * D:
+        raise ValueError("qknorm_rope_kv_append: qkv must be contiguous [N, (nq+2nkv)*D]")
+    if positions.dtype != torch.int32 or positions.numel() != Ntok or not positions.is_contiguous():
+        raise ValueError("qknorm_rope_kv_append: positions must be contiguous int32 [N]")
+    for w in (qn, kn):
+        if tuple(w.shape) != (D,) or w.dtype != qkv.dtype or w.device != qkv.device or not w.is_contiguous():
+            raise ValueError("qknorm_rope_kv_append: the norm weights must be contiguous [D] tensors of qkv's dtype and device")
+    R = Ntok // T
+    G = nq // nkv
+    q = torch.empty((R, nkv, G * T, D), dtype=qkv.dtype, device=qkv.device)
+    S_max = k_cache.shape[2]
+    T_max = k_cand.shape[2] if k_cand is not None else 0
+    N.check(N.lib().jf_qknorm_rope_kv_append(_ptr(qkv), _dtype_code(qkv), Ntok, T, nq, nkv, D, _ptr(qn), _ptr(kn), float(eps),
+                                             _ptr(positions), _ptr(cos), _ptr(sin), _ptr(q), _ptr(k_cache), _ptr(v_cache),
+                                             _ptr(slot_main), S_max, _ptr(k_cand) if slot_cand is not None else None,
+                                             _ptr(v_cand) if slot_cand is not None else None, _ptr(slot_cand), T_max,
+                                             _stream(qkv.device)), "jf_qknorm_rope_kv_append")
+    return q
+
+
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     """silu(gate) * up for the fused [M, 2I] projection output -> [M, I] (one HIP launch)."""
     if gu.dim() != 2 or not gu.is_contiguous() or gu.shape[1] % 2:
